@@ -2,8 +2,12 @@
 """Headline benchmark: images/sec of SD1.5-shaped 512x512, 50-step `etainv + ptp` (forward DDIM inversion +
 eta-scheduled backward edit with prompt-to-prompt attention control), batch-sharded over N GPUs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dtype fp16|bf16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dtype fp16|bf16] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs if `--dump-outputs` is given and prints the line.
+`--full` adds what takes work of its own: the per-kernel-class roofline figures of one extra profiled step, the executed-FLOP figures
+derived from it, the PMC figures read from profiles/ and the CPU-oracle baseline (unless `--no-cpu-baseline`).
 
 One "step" = the whole hot path over one batch of B synthetic image pairs per GPU: 50 forward UNet calls (B rows:
 the uncond half is skipped because guidance_scale_fwd == 1 multiplies it out) + 50 backward UNet calls (4B rows) +
@@ -44,6 +48,22 @@ CONFIGS = {
 }
 MFMA_PEAK_TFLOPS = 2500.0       # dense fp16/bf16 (MI355X_MICROARCH.md)
 HBM_PEAK_GBS = 8000.0
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: all files together, .npy headers included
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """Write every array of `arrays` (name -> tensor or None) as `<out_dir>/<name>.npy` in float32.  When their sum would pass
+    DUMP_LIMIT_BYTES, each array is replaced by the same share of its flattened elements, drawn without replacement by a fixed seed and kept
+    in index order, so that two runs with the same arguments write comparable files."""
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items() if v is not None}
+    budget = DUMP_LIMIT_BYTES - 1024 * len(arrays)                        # (an .npy header is 128 bytes)
+    total = 4 * sum(v.size for v in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for i, (name, v) in enumerate(arrays.items()):
+        if total > budget:
+            keep = v.size * budget // total
+            v = v.reshape(-1)[np.sort(np.random.default_rng(seed + i).choice(v.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(v, dtype=np.float32))
 
 
 def ptp_tables(B, S):
@@ -203,6 +223,7 @@ def stub_main(a, world, rank):
         if on:
             gathered = [torch.empty_like(out) for _ in range(world)]
             dist.all_gather(gathered, out)
+            out = torch.cat(gathered)
         return out
 
     for _ in range(a.warmup):
@@ -211,7 +232,7 @@ def stub_main(a, world, rank):
         dist.barrier()
     t0 = time.time()
     for _ in range(a.steps):
-        one_step()
+        out = one_step()
     if on:
         dist.barrier()
     dt = time.time() - t0
@@ -219,6 +240,8 @@ def stub_main(a, world, rank):
         tmax = torch.tensor([dt])
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"stub_output": out})
     if rank == 0:
         print(json.dumps({"metric": "stub", "value": a.batch * world * a.steps / max(dt, 1e-9), "unit": "images/s", "n_gpus": world, "steps": a.steps,
                           "warmup": a.warmup, "ms_per_step": 1e3 * dt / a.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -269,12 +292,19 @@ def main():
     ap.add_argument("--config", type=int, default=3, choices=sorted(CONFIGS), help="BASELINE.json configuration (3 = the headline metric)")
     ap.add_argument("--batch", type=int, default=None, help="image pairs per GPU per step (default: the configuration's)")
     ap.add_argument("--dtype", default=None, choices=["fp16", "bf16"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also the roofline figures of one extra profiled step, the PMC figures of profiles/ and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, rank 0): edited_latents (the all-gathered "
+                         "(2B,4,L,L) [source, target] rows of every rank), inversion_latents (rank 0's forward trajectory at steps 0, 10, ..., S) and "
+                         "word_maps (rank 0's mean word maps, ptp only)")
     ap.add_argument("--with-nets", action="store_true", help="add a secondary figure: image -> image BatchEditor.edit (VAE encode, CLIP, loop, 2 VAE decodes)")
     ap.add_argument("--all-rows", action="store_true", help="run every UNet row the reference's call pattern has in the backward pass (250 sample-forwards per image: "
                                                            "no dead-row skipping, no early exit of the cond source rows) -- for A/B; the default is the engine as shipped")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)   # tests only: launcher / rank protocol over gloo, no engine, no GPU
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     cfg = CONFIGS[a.config]
     if a.all_rows:                                 # the reference's backward row count AND every row through every layer (no shared prefix)
         os.environ["ETAINV_NO_DEAD_ROW_SKIP"] = "1"
@@ -326,7 +356,6 @@ def main():
     from etainv import _capi
     from etainv.engine import Engine
     from etainv.pipeline import EtaLoop, noise_table
-    lib = _capi.load()
     B = a.batch
     dtype = {"fp16": torch.float16, "bf16": torch.bfloat16}[a.dtype]
     eng = Engine(dtype=dtype, max_unet_batch=4 * B, latent_size=L, max_img=B, device=str(dev))
@@ -340,10 +369,11 @@ def main():
     def one_step():
         inv = loop.invert(z0, ctx_src, tokens)
         out = loop.sample(inv, ctx_src, ctx_tgt, noise, edit_word=edit_word, ptp=tables, masactrl=masa)
+        gathered = None
         if dist is not None:       # the path's only exchange: final gather of the edited latents (32 KiB / image)
             gathered = [torch.empty_like(out) for _ in range(world)]
             dist.all_gather(gathered, out)
-        return out
+        return inv, out, gathered
 
     def barrier():
         if dist is not None:
@@ -356,7 +386,7 @@ def main():
     rows0 = loop.rows_executed
     t0 = time.time()
     for _ in range(a.steps):
-        out = one_step()
+        inv, out, gathered = one_step()
     barrier()
     dt = time.time() - t0
     # UNet sample-forwards the timed steps actually issued per image: S cond rows forward + 4 per backward step, minus the uncond source row of the
@@ -368,74 +398,81 @@ def main():
         tmax = torch.tensor([dt], device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
-    with_nets = None
-    if a.with_nets and cfg["editor"] == "ptp":
-        with_nets = nets_figure(eng, dtype, B, S_STEPS, L, dev, max(1, min(a.steps, 3)))
-    # per-kernel-class HIP-event timing (roofline fields) on ONE extra step OUTSIDE the timed region: the events sit on the launch
-    # stream around every launch and would otherwise add their own (small) cost to `value`
-    lib.etainv_prof_reset()
-    lib.etainv_prof_enable(1)
-    tp0 = time.time()
-    one_step()
-    torch.cuda.synchronize()
-    dt_prof = time.time() - tp0
-    lib.etainv_prof_enable(0)
-
-    def prof(cls):
-        ms, work, n = C.c_double(), C.c_double(), C.c_int64()
-        _capi.check(lib.etainv_prof_read(cls, C.byref(ms), C.byref(work), C.byref(n)))
-        return ms.value, work.value, n.value
-
-    ig_ms, ig_flop, ig_n = prof(0)
-    sa_ms, sa_flop, sa_n = prof(1)
-    ca_ms, ca_flop, ca_n = prof(2)
-    gn_ms, gn_bytes, gn_n = prof(3)
-    ln_ms, ln_bytes, ln_n = prof(4)
-    split, split_n = (C.c_double * 6)(), (C.c_int64 * 2)()
-    ridge = MFMA_PEAK_TFLOPS * 1e12 / (HBM_PEAK_GBS * 1e9)          # 312.5 FLOP per byte
-    _capi.check(lib.etainv_prof_split(0, ridge, split, split_n))
-    # fabric-side bytes per igemm launch: a PMC figure (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes over tools/unet_call.py
-    # --rows 128, FETCH_SIZE x2 per MI355X_MICROARCH.md, aggregated by tools/pmc_traffic.py), NOT measured by this run: the file is named
-    # in the JSON and belongs to the kernels of the round it was taken in
-    # (taken at 128 UNet rows = the default workload; null for the other configurations, whose launches have other sizes)
-    # A file is used only when its `kernel_src_sha16` (tools/srcstamp.py: hash of csrc/ + include/etainv.h, written by the aggregators) equals that of the
-    # sources this run was built from; otherwise the field is null and `*_source` says which file was stale.
-    sys.path.insert(0, str(ROOT / "tools"))
-    from srcstamp import kernel_src_sha16, stamped_figure
-    src_sha = kernel_src_sha16()
-    traffic = traffic_src = mfma_busy = mfma_busy_src = None
-    if 4 * B == 128:
-        traffic, traffic_src = stamped_figure(ROOT / "profiles", "r*_pmc_traffic_rows128.json", src_sha, lambda d: d.get("igemm", {}).get("hbm_bytes_per_launch"),
-                                              "fabric bytes per implicit-GEMM launch of one 128-row UNet call")
-        # matrix-pipe busy share of the same kernels from the SQ counters (rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES / GRBM_GUI_ACTIVE over tools/unet_call.py
-        # --rows 128, aggregated by tools/pmc_sq.py): file-sourced like `traffic`, named in the JSON
-        mfma_busy, mfma_busy_src = stamped_figure(ROOT / "profiles", "r*_pmc_sq_rows128.json", src_sha, lambda d: (d.get("summary", {}).get("igemm_family") or {}).get("mfma_busy_frac"),
-                                                  "cycle-weighted MFMA-busy share of the implicit-GEMM kernels over one 128-row UNet call")
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"edited_latents": out if gathered is None else torch.cat(gathered),
+                                      "inversion_latents": inv["latents"][sorted(set(range(0, S_STEPS + 1, 10)) | {S_STEPS})],
+                                      "word_maps": inv["maps_mean"]})
     images = B * world * a.steps
     value = images / dt
-    # MFMA FLOPs the kernels EXECUTED per image (implicit GEMMs + both attentions of the profiled step: the launchers record 2 M N K / 4 B h N^2 d
-    # of every launch), i.e. after dead rows, early exits and the shared context-independent prefix -- not a row count times a constant
-    exec_tflop_per_image = (ig_flop + sa_flop + ca_flop) / B / 1e12
-    if rank == 0:
+    line = {
+        "metric": f"images/sec SD1.5 {8 * L}^2 {S_STEPS}-step {cfg['name']}", "value": value, "unit": "images/s", "n_gpus": world,
+        "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * dt / a.steps, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
+        "config": {"workload": f"{cfg['name']}, SD1.5-shaped UNet (seeded synthetic weights), {8 * L}x{8 * L} ({L}x{L} latents), {S_STEPS} DDIM steps, "
+                               f"{B} image pairs per GPU per step, eta {cfg['eta']}, n=10 noise candidates, cfg 7.5/1",
+                   "baseline_config": a.config,
+                   "images_per_gpu": B, "unet_sample_forwards_per_image": FWD_PER_IMAGE,
+                   "unet_sample_forwards_per_image_reference": 6 * S_STEPS,
+                   "row_economy": "executed count = S cond rows forward (guidance_scale_fwd == 1 multiplies the uncond half out) + per backward step 4 rows while eta(t) > 0, "
+                                  "3 rows [u_t, c_s, c_t] while eta(t) == 0 (the source row is replayed and its guided noise only picks a noise sample that is multiplied by "
+                                  "eta = 0), the cond source row leaving the UNet after transformer block 12 / 9 once no cross replacement / no self-replace reads it; same edited "
+                                  "latents (tests/test_e2e_gpu.py, profiles/r03_parity_S50.json); `--all-rows` runs 5 S rows per image",
+                   "sharding": f"batch-shard x{world}, final all_gather of latents"},
+    }
+    if a.with_nets and cfg["editor"] == "ptp":
+        line["with_nets"] = nets_figure(eng, dtype, B, S_STEPS, L, dev, max(1, min(a.steps, 3)))
+    if a.full:
+        # per-kernel-class HIP-event timing (roofline fields) on ONE extra step OUTSIDE the timed region: the events sit on the launch
+        # stream around every launch and would otherwise add their own (small) cost to `value`
+        lib = _capi.load()
+        lib.etainv_prof_reset()
+        lib.etainv_prof_enable(1)
+        tp0 = time.time()
+        one_step()
+        torch.cuda.synchronize()
+        dt_prof = time.time() - tp0
+        lib.etainv_prof_enable(0)
+
+        def prof(cls):
+            ms, work, n = C.c_double(), C.c_double(), C.c_int64()
+            _capi.check(lib.etainv_prof_read(cls, C.byref(ms), C.byref(work), C.byref(n)))
+            return ms.value, work.value, n.value
+
+        ig_ms, ig_flop, ig_n = prof(0)
+        sa_ms, sa_flop, sa_n = prof(1)
+        ca_ms, ca_flop, ca_n = prof(2)
+        gn_ms, gn_bytes, gn_n = prof(3)
+        ln_ms, ln_bytes, ln_n = prof(4)
+        split, split_n = (C.c_double * 6)(), (C.c_int64 * 2)()
+        ridge = MFMA_PEAK_TFLOPS * 1e12 / (HBM_PEAK_GBS * 1e9)          # 312.5 FLOP per byte
+        _capi.check(lib.etainv_prof_split(0, ridge, split, split_n))
+        # fabric-side bytes per igemm launch: a PMC figure (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes over tools/unet_call.py
+        # --rows 128, FETCH_SIZE doubled for gfx950's wide streaming reads, aggregated by tools/pmc_traffic.py), NOT measured by this run: the file is named
+        # in the JSON and belongs to the kernels of the round it was taken in
+        # (taken at 128 UNet rows = the default workload; null for the other configurations, whose launches have other sizes)
+        # A file is used only when its `kernel_src_sha16` (tools/srcstamp.py: hash of csrc/ + include/etainv.h, written by the aggregators) equals that of the
+        # sources this run was built from; otherwise the field is null and `*_source` says which file was stale.
+        sys.path.insert(0, str(ROOT / "tools"))
+        from srcstamp import kernel_src_sha16, stamped_figure
+        src_sha = kernel_src_sha16()
+        traffic = traffic_src = mfma_busy = mfma_busy_src = None
+        if 4 * B == 128:
+            traffic, traffic_src = stamped_figure(ROOT / "profiles", "r*_pmc_traffic_rows128.json", src_sha, lambda d: d.get("igemm", {}).get("hbm_bytes_per_launch"),
+                                                  "fabric bytes per implicit-GEMM launch of one 128-row UNet call")
+            # matrix-pipe busy share of the same kernels from the SQ counters (rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES / GRBM_GUI_ACTIVE over tools/unet_call.py
+            # --rows 128, aggregated by tools/pmc_sq.py): file-sourced like `traffic`, named in the JSON
+            mfma_busy, mfma_busy_src = stamped_figure(ROOT / "profiles", "r*_pmc_sq_rows128.json", src_sha, lambda d: (d.get("summary", {}).get("igemm_family") or {}).get("mfma_busy_frac"),
+                                                      "cycle-weighted MFMA-busy share of the implicit-GEMM kernels over one 128-row UNet call")
+        # MFMA FLOPs the kernels EXECUTED per image (implicit GEMMs + both attentions of the profiled step: the launchers record 2 M N K / 4 B h N^2 d
+        # of every launch), i.e. after dead rows, early exits and the shared context-independent prefix -- not a row count times a constant
+        exec_tflop_per_image = (ig_flop + sa_flop + ca_flop) / B / 1e12
         achieved = ig_flop / (ig_ms * 1e-3) / 1e12 if ig_ms > 0 else 0.0
-        line = {
-            "metric": f"images/sec SD1.5 {8 * L}^2 {S_STEPS}-step {cfg['name']}", "value": value, "unit": "images/s", "n_gpus": world,
-            "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * dt / a.steps, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
-            "config": {"workload": f"{cfg['name']}, SD1.5-shaped UNet (seeded synthetic weights), {8 * L}x{8 * L} ({L}x{L} latents), {S_STEPS} DDIM steps, "
-                                   f"{B} image pairs per GPU per step, eta {cfg['eta']}, n=10 noise candidates, cfg 7.5/1",
-                       "baseline_config": a.config,
-                       "images_per_gpu": B, "unet_sample_forwards_per_image": FWD_PER_IMAGE,
-                       "unet_sample_forwards_per_image_reference": 6 * S_STEPS,
-                       "row_economy": "executed count = S cond rows forward (guidance_scale_fwd == 1 multiplies the uncond half out) + per backward step 4 rows while eta(t) > 0, "
-                                      "3 rows [u_t, c_s, c_t] while eta(t) == 0 (the source row is replayed and its guided noise only picks a noise sample that is multiplied by "
-                                      "eta = 0), the cond source row leaving the UNet after transformer block 12 / 9 once no cross replacement / no self-replace reads it; same edited "
-                                      "latents (tests/test_e2e_gpu.py, profiles/r03_parity_S50.json); `--all-rows` runs 5 S rows per image",
-                       "tflop_per_image": exec_tflop_per_image,
-                       "tflop_per_image_note": "executed MFMA FLOPs (sum over the launches of one step, after row skipping, early exits and prefix sharing); "
-                                               f"row count x {F_UNET_TFLOP} TFLOP would give {FWD_PER_IMAGE * F_UNET_TFLOP:.1f}, the reference's call pattern "
-                                               f"{6 * S_STEPS * F_UNET_TFLOP:.1f}",
-                       "sharding": f"batch-shard x{world}, final all_gather of latents"},
+        line["config"].update({
+            "tflop_per_image": exec_tflop_per_image,
+            "tflop_per_image_note": "executed MFMA FLOPs (sum over the launches of one step, after row skipping, early exits and prefix sharing); "
+                                    f"row count x {F_UNET_TFLOP} TFLOP would give {FWD_PER_IMAGE * F_UNET_TFLOP:.1f}, the reference's call pattern "
+                                    f"{6 * S_STEPS * F_UNET_TFLOP:.1f}"})
+        line.update({
             "end_to_end_mfma_frac": value / world * exec_tflop_per_image / MFMA_PEAK_TFLOPS,
             "roofline": {"bound": "mfma", "kernel": "implicit-GEMM family: pp_conv2_kernel / pp_conv_kernel (conv3x3, PATCH ping-pong, dual-M / 256-pixel tiles), pp_dualn_kernel (1x1 / Linear / GEGLU, dual-N "
                                                     "ping-pong), igemm_kernel (strided / upsampling / small launches)", "achieved": achieved,
@@ -460,11 +497,10 @@ def main():
                               "share_of_wall": gn_ms * 1e-3 / dt_prof, "launches": gn_n},
                 "layernorm": {"gbs": ln_bytes / max(ln_ms, 1e-9) / 1e6, "frac_hbm": ln_bytes / max(ln_ms, 1e-9) / 1e6 / HBM_PEAK_GBS,
                               "share_of_wall": ln_ms * 1e-3 / dt_prof, "launches": ln_n}},
-        }
-        if with_nets is not None:
-            line["with_nets"] = with_nets
-        if world == 1 and not a.no_cpu_baseline and a.config == 3:
+        })
+        if world == 1 and not a.no_cpu_baseline and a.config == 3 and rank == 0:
             line["cpu_baseline"] = cpu_baseline()
+    if rank == 0:
         print(json.dumps(line))
     if dist is not None:
         dist.destroy_process_group()

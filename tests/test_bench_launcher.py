@@ -38,3 +38,35 @@ def test_launcher_relays_a_failing_child():
         pytest.skip("needs a GPU-less host")
     r = run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"])
     assert r.returncode != 0 and not r.stdout.strip()
+
+
+def test_dump_outputs_same_arguments_same_files(tmp_path):
+    # --dump-outputs: the last timed step's output as float32 .npy (here the all-gathered stub rows of both ranks); same arguments, same inputs
+    import numpy as np
+    for d in ("a", "b"):
+        r = run(["--gpus", "2", "--stub", "--steps", "2", "--warmup", "1", "--batch", "3", "--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+    a, b = np.load(tmp_path / "a" / "stub_output.npy"), np.load(tmp_path / "b" / "stub_output.npy")
+    assert a.dtype == np.float32 and a.shape == (6, 4, 8, 8) and np.array_equal(a, b)
+    assert not np.array_equal(a[:3], a[3:])                        # the two ranks' rows (seeded per rank) are both there
+
+
+def test_dump_outputs_samples_past_the_limit(tmp_path, monkeypatch):
+    # past DUMP_LIMIT_BYTES every array keeps the same share of its elements, at seeded positions in index order: the files stay under the
+    # limit and two dumps of the same arrays are equal
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 64 << 10)
+    arrays = {"x": torch.arange(40000, dtype=torch.float32).reshape(200, 200), "y": torch.ones(1000, dtype=torch.float64), "absent": None}
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, arrays)
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["x.npy", "y.npy"]
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 64 << 10
+    x, y = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "a" / "y.npy")
+    assert x.dtype == y.dtype == np.float32 and 0 < x.size < 40000 and 0 < y.size < 1000
+    assert np.all(np.diff(x) > 0) and np.all(y == 1)
+    assert np.array_equal(x, np.load(tmp_path / "b" / "x.npy"))
+    small = {"z": torch.linspace(0, 1, 100)}
+    bench.dump_outputs(tmp_path / "c", small)
+    assert np.array_equal(np.load(tmp_path / "c" / "z.npy"), small["z"].numpy())

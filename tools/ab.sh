@@ -13,8 +13,8 @@
 #   counters                   rocprofv3 -L -> counters.txt
 #   opsenv2 <only> <envA> <envB> same-box A/B of the default library under two environments
 #   opslib <only> <variant>    same-box A/B: libetainv_hip.so vs libetainv_hip_<variant>.so (built by csrc/build.sh VARIANT=...)
-#   bench [args]               python bench.py [args] (default invocation when no args) -> bench<sanitised args>.json
-#   benchenv <envB> [n]        bench A/B (--steps 2 --warmup 1 --no-cpu-baseline), n alternations (default 2)
+#   bench [args]               python bench.py --full [args] -> bench<sanitised args>.json
+#   benchenv <envB> [n]        bench A/B (--full --steps 2 --warmup 1 --no-cpu-baseline), n alternations (default 2)
 #   stats                      rocprofv3 --kernel-trace --stats of one bench step -> kernel_stats_b32.csv
 #   pytest [args]              python -m pytest tests -m gpu -x -q [args] -> gpu_suite.log
 #   py <file> [args]           python <file> [args] -> <basename>.log
@@ -102,15 +102,15 @@ PYEOF
       echo "A = default, B = variant $2"; cat $OUT/opslib_$1_$2.log ;;
     bench)
       local name="bench$(echo "$*" | tr -c 'A-Za-z0-9\n' '_')"
-      python bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err; pyjson "$name" < $OUT/$name.json ;;
+      python bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err; pyjson "$name" < $OUT/$name.json ;;
     benchenv)
       local n="${2:-2}"
       for i in $(seq $n); do
-        python bench.py --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | tee $OUT/benchenv_a_$i.json | pyjson "A default"
-        env ${1//,/ } python bench.py --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | tee $OUT/benchenv_b_$i.json | pyjson "B $1"
+        python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | tee $OUT/benchenv_a_$i.json | pyjson "A default"
+        env ${1//,/ } python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | tee $OUT/benchenv_b_$i.json | pyjson "B $1"
       done ;;
     stats)
-      rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_b32 -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline > $OUT/bench_b32_under_rocprof.json 2> $OUT/prof_b32.err
+      rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_b32 -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline > $OUT/bench_b32_under_rocprof.json 2> $OUT/prof_b32.err
       find $OUT/prof_b32 -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats_b32.csv \;
       rm -rf $OUT/prof_b32; head -8 $OUT/kernel_stats_b32.csv ;;
     pytest)

@@ -8,4 +8,4 @@ for f in bench_b32_under_rocprof.json bench_cfg2.json bench_cfg5.json bench_defa
          pmc_per_shape_rows128.json pmc_sq_rows128.json pmc_traffic_rows128.json smoke.log unet_shapes_rows128.log unet_shapes_rows32.log unet_shapes_rows32_L96.log; do
   cp "$O/$f" "profiles/${PFX}_$f"
 done
-echo "published $O -> profiles/${PFX}_*  (stamp $(python tools/srcstamp.py); now take the stamped bench: gpurun -- 'python bench.py > gpurun_out/bench_stamped.json')"
+echo "published $O -> profiles/${PFX}_*  (stamp $(python tools/srcstamp.py); now take the stamped bench on the GPU box: python bench.py --full)"
