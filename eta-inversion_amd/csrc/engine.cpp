@@ -1316,6 +1316,38 @@ extern "C" int etainv_op_gemm_ln(const void* a, const void* w_folded, const floa
   return launch_igemm(p, dtype, (hipStream_t)stream, stat_p_out);
 }
 
+// the fused QKV projection as transformer() launches it: head-major planes [q|k|v][row][head][token][head_dim] when igemm_hm_ok allows (*wrote_head_major = 1),
+// the row-major LayerNorm-consumer GEMM of etainv_op_gemm_ln otherwise (0)
+extern "C" int etainv_op_gemm_ln_hm(const void* a, const void* w_folded, const float* c_vec, const float* s_vec, const float* stat, void* out, int m, int n,
+                                    int k, int heads, int head_dim, int tokens, int* wrote_head_major, int dtype, void* stream) {
+  ETAINV_CHECK(stat && s_vec && c_vec && wrote_head_major, "the LayerNorm-consumer GEMM needs stat, s_vec, c_vec and wrote_head_major");
+  IGemmParams p;
+  p.a1 = a;
+  p.w = w_folded;
+  p.bias = c_vec;
+  p.out = out;
+  p.M = m;
+  p.N = n;
+  p.c1 = k;
+  p.W = m;
+  p.Wo = m;
+  p.rows_per_batch = m;
+  p.ln_stat = stat;
+  p.ln_s = s_vec;
+  *wrote_head_major = 0;
+  if (self_attn_head_major_ok(head_dim, dtype)) {
+    IGemmParams q = p;
+    q.hm_heads = heads;
+    q.hm_dim = head_dim;
+    q.hm_tokens = tokens;
+    if (igemm_hm_ok(q, dtype)) {
+      *wrote_head_major = 1;
+      return launch_igemm(q, dtype, (hipStream_t)stream);
+    }
+  }
+  return launch_igemm(p, dtype, (hipStream_t)stream);
+}
+
 extern "C" int etainv_op_gemm_gnstat(const void* a, const void* w, const float* bias, const void* residual, void* out, float* part, int* wm_out, int m,
                                      int n, int k, int rows_per_image, int dtype, void* stream) {
   IGemmParams p;
@@ -1454,6 +1486,12 @@ extern "C" int etainv_experiments_built = 1;   // data symbol (not part of the A
 extern "C" int etainv_op_self_attention(const void* qkv, void* out, int b, int n, int heads, int d, int mode, int n_img, int dtype,
                                         void* stream) {
   return launch_self_attention_mode(qkv, out, b, n, heads, d, mode, n_img, dtype, (hipStream_t)stream);
+}
+
+// every argument of the launcher (the engine's form: q_prescaled = 1 at head_dim 40 / 80, head-major planes, the three-row layouts through first_row)
+extern "C" int etainv_op_self_attention_ex(const void* qkv, void* out, int b, int n, int heads, int d, int mode, int n_img, int q_prescaled, int first_row,
+                                           int head_major, int dtype, void* stream) {
+  return launch_self_attention_mode(qkv, out, b, n, heads, d, mode, n_img, dtype, (hipStream_t)stream, q_prescaled, first_row, head_major);
 }
 
 extern "C" int etainv_op_cross_attention(const void* q, const void* kv, void* out, int b, int n, int heads, int d, int n_ctx,

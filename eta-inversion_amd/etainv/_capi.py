@@ -64,6 +64,7 @@ SIGNATURES = {
     "etainv_prof_split": [_i, C.c_double, C.POINTER(C.c_double), C.POINTER(_i64)],
     "etainv_op_gemm": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "etainv_op_gemm_ln": [_p, _p, _p, _p, _p, _p, _p, _p, C.POINTER(_i), _i, _i, _i, _i, _i, _p],
+    "etainv_op_gemm_ln_hm": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, C.POINTER(_i), _i, _p],
     "etainv_engine_cache_context": [_p, _i],
     "etainv_engine_context_generation": [_p, C.c_uint64],
     "etainv_op_gemm_gnstat": [_p, _p, _p, _p, _p, _p, C.POINTER(_i), _i, _i, _i, _i, _i, _p],
@@ -83,6 +84,7 @@ SIGNATURES = {
     "etainv_op_groupnorm": [_p, _p, _i, _i, _p, _p, _p, _i, _i, _i, _f, _i, _p, _i, _p],
     "etainv_op_layernorm": [_p, _p, _p, _p, _i, _i, _f, _i, _p],
     "etainv_op_self_attention": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
+    "etainv_op_self_attention_ex": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "etainv_op_cross_attention": [_p, _p, _p, _i, _i, _i, _i, _i, C.POINTER(AttnCtrl), _i, _i, _p, _i, _p],
     "etainv_op_word_maps": [_p, _i, _i, _i, _i, _i, _i, _p, _i, _i, _p, _i, _f, _p],
     "etainv_op_local_blend": [_p, _i, _i, _i, _i, _i, _p, _i, _p, _f, _p],

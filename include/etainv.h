@@ -250,6 +250,10 @@ int etainv_op_gemm(const void* a, const void* w, const void* bias, const void* r
 int etainv_op_gemm_ln(const void* a, const void* w_folded, const float* c_vec, const float* s_vec, const float* stat,
                       const void* residual, void* out, float* stat_out, int* stat_p_out, int m, int n, int k, int geglu,
                       int dtype, void* stream);
+/* The LayerNorm-consumer GEMM above as the fused QKV projection of a transformer block launches it: where the launch shape allows, out is written as
+ * three head-major planes [q|k|v][m / tokens][heads][tokens][head_dim] (*wrote_head_major = 1), otherwise row-major [m][n] (0).  n == 3 heads head_dim. */
+int etainv_op_gemm_ln_hm(const void* a, const void* w_folded, const float* c_vec, const float* s_vec, const float* stat, void* out,
+                         int m, int n, int k, int heads, int head_dim, int tokens, int* wrote_head_major, int dtype, void* stream);
 /* W' = gamma . W (packed, compute dtype; geglu: the value / gate row interleave of the GEGLU projection), s = row sums of the rounded W',
  * c = beta W^T + bias (bias in logical row order, may be NULL) */
 int etainv_op_ln_fold(const float* w, const float* gamma, const float* beta, const float* bias, int n, int k, int geglu, float scale,
@@ -300,6 +304,11 @@ int etainv_op_layernorm(const void* x, const float* gamma, const float* beta, vo
 /* mode 0 plain, 1 ptp self-replace, 2 masactrl (modes 1/2: b == 4*n_img rows [u_s,u_t,c_s,c_t]) */
 int etainv_op_self_attention(const void* qkv, void* out, int b, int n, int heads, int d, int mode, int n_img,
                              int dtype, void* stream);
+/* The same launch with every argument the UNet passes.  q_prescaled: the queries already carry head_dim^-0.5 * log2(e) (head_dim 40 / 80, 16-bit types);
+ * first_row: 0 = all 4 n_img rows, n_img = rows [u_t, c_s, c_t] (mode 1), < 0 = rows [u_t, c_t, c_s] (mode 1, b == 3 n_img; see etainv_attn_ctrl);
+ * head_major: qkv holds three planes [q|k|v][b][heads][n][d] instead of rows [b][n][3 heads d] (head_dim 40 / 80, 16-bit types; else an error). */
+int etainv_op_self_attention_ex(const void* qkv, void* out, int b, int n, int heads, int d, int mode, int n_img,
+                                int q_prescaled, int first_row, int head_major, int dtype, void* stream);
 int etainv_op_cross_attention(const void* q, const void* kv, void* out, int b, int n, int heads, int d,
                               int n_ctx, const etainv_attn_ctrl* ctrl, int map_layer, int n_img_cap,
                               float* maps_acc, int dtype, void* stream);

@@ -11,6 +11,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import attention_ref as AR
+
 pytestmark = pytest.mark.gpu
 
 DTYPES = [torch.float16, torch.bfloat16]
@@ -788,18 +790,24 @@ def test_layernorm(capi, dtype, rows, c):
 
 
 # ----------------------------------------------------------------------------------------- attention
+# Every self-attention test asserts three bounds (tests/attention_ref.py: check_attention): the global relative L2 error below TOL as before, the worst
+# (row, head, 32-query block) below TOL too, and the worst single query below 2 x TOL -- a wrong item hides in a global norm.  tests/test_attention_ref.py shows
+# on the CPU that rounding P and the output to the operand type alone stays below half of each bound on every input family used here.
 def ref_self_attention(qkv, heads, qmap=None, kmap=None, vmap=None):
-    b, n, c3 = qkv.shape
-    c = c3 // 3
-    d = c // heads
-    q, k, v = qkv.float().split(c, dim=-1)
-    idx = torch.arange(b)
-    q = q[idx if qmap is None else qmap]
-    k = k[idx if kmap is None else kmap]
-    v = v[idx if vmap is None else vmap]
-    sp = lambda t: t.reshape(b, n, heads, d).permute(0, 2, 1, 3)
-    a = (sp(q) @ sp(k).transpose(-1, -2) * d ** -0.5).softmax(-1)
-    return (a @ sp(v)).permute(0, 2, 1, 3).reshape(b, n, c)
+    return AR.ref_self_attention(qkv, heads, qmap, kmap, vmap)
+
+
+def n_cu():
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def _check(out, qkv, heads, d, maps=(None, None, None), factor=1.0, label=""):
+    """the three bounds against the fp32 reference of the same input; returns the reference"""
+    ref = AR.ref_self_attention(qkv, heads, *maps)
+    assert torch.isfinite(out).all()
+    route = AR.self_attention_route(qkv.shape[0], qkv.shape[1], heads, d, n_cu()) if qkv.dtype != torch.float32 else "fp32"
+    AR.check_attention(out, ref, heads, d, qkv.dtype, factor, f"{label} route={route}", emulate=lambda: AR.emulate_16bit(qkv, heads, *maps))
+    return ref
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -810,7 +818,7 @@ def test_self_attention_plain(capi, dtype, n, d):
     qkv = rnd(b, n, 3 * heads * d, seed=1, dtype=dtype)
     out = torch.empty(b, n, heads * d, dtype=dtype, device="cuda")
     capi.check(lib.etainv_op_self_attention(capi.ptr(qkv), capi.ptr(out), b, n, heads, d, 0, 1, capi.dtype_code(dtype), capi.stream_ptr()))
-    assert relerr(out, ref_self_attention(qkv, heads)) < TOL[dtype]
+    _check(out, qkv, heads, d, label="plain")
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -826,8 +834,7 @@ def test_self_attention_d40(capi, dtype, n, b, heads, gain):
     qkv[..., : 2 * heads * d] *= gain
     out = torch.empty(b, n, heads * d, dtype=dtype, device="cuda")
     capi.check(lib.etainv_op_self_attention(capi.ptr(qkv), capi.ptr(out), b, n, heads, d, 0, 1, capi.dtype_code(dtype), capi.stream_ptr()))
-    assert torch.isfinite(out).all()
-    assert relerr(out, ref_self_attention(qkv, heads)) < TOL[dtype] * (2 if gain > 1 else 1)
+    _check(out, qkv, heads, d, factor=2 if gain > 1 else 1, label=f"d40 gain={gain}")
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -840,8 +847,7 @@ def test_self_attention_d80(capi, dtype, n, b, heads, gain):
     qkv[..., : 2 * heads * d] *= gain
     out = torch.empty(b, n, heads * d, dtype=dtype, device="cuda")
     capi.check(lib.etainv_op_self_attention(capi.ptr(qkv), capi.ptr(out), b, n, heads, d, 0, 1, capi.dtype_code(dtype), capi.stream_ptr()))
-    assert torch.isfinite(out).all()
-    assert relerr(out, ref_self_attention(qkv, heads)) < TOL[dtype] * (2 if gain > 1 else 1)
+    _check(out, qkv, heads, d, factor=2 if gain > 1 else 1, label=f"d80 gain={gain}")
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -856,32 +862,26 @@ def test_self_attention_d160(capi, dtype, n, b, heads, gain, mode):
     qkv[..., : 2 * heads * d] *= gain
     out = torch.empty(b, n, heads * d, dtype=dtype, device="cuda")
     capi.check(lib.etainv_op_self_attention(capi.ptr(qkv), capi.ptr(out), b, n, heads, d, mode, n_img, capi.dtype_code(dtype), capi.stream_ptr()))
-    ident = torch.arange(b)
-    qm, km, vm = ident.clone(), ident.clone(), ident.clone()
-    for img in range(n_img if mode else 0):
-        u_s, u_t, c_s, c_t = img, n_img + img, 2 * n_img + img, 3 * n_img + img
-        if mode == 1:
-            qm[c_t], km[c_t] = c_s, c_s
-        else:
-            km[u_t], vm[u_t], km[c_t], vm[c_t] = u_s, u_s, c_s, c_s
-    assert torch.isfinite(out).all()
-    assert relerr(out, ref_self_attention(qkv, heads, qm, km, vm)) < TOL[dtype] * (2 if gain > 1 else 1)
+    _check(out, qkv, heads, d, AR.row_maps(b, n_img, mode, 0), factor=2 if gain > 1 else 1, label=f"d160 gain={gain} mode={mode}")
 
 
 def test_self_attention_d40_maximum_jumps_late(capi):
     """A key whose score exceeds everything before it by far more than the deferral threshold, placed in a LATE tile, for a few queries
-    only (the branch is wave-uniform, the update per query), plus a first tile whose scores are all very negative for other queries."""
+    only (the branch is wave-uniform, the update per query), plus a first tile whose scores are all very negative for other queries.
+    The single-query bound is taken against the reference of the ROUNDED scaled queries: with q_prescaled = 0 the kernel multiplies Q by d^-0.5 log2 e and rounds
+    the product to the MFMA's 16-bit operand type; the planted keys (|k| = 6 |q|, 8 |q|) give every query scores of tens of nats, a relative 2^-11 of which moves
+    single softmax rows by more than 2 x TOL (measured on the device: query 75 of head 5 at 4.63e-3 against the exact reference; EXACT attention on the rounded
+    queries differs from it by 4.5e-3 at the same query: test_attention_ref.py::test_scaled_query_rounding_on_maximum_jumps_late).  In the engine's form that
+    rounding is the to_q projection's.  Global, per-block and the hand-picked queries stay against the exact reference."""
     lib = capi.load()
     b, heads, n, d, dtype = 1, 8, 512, 40, torch.float16
-    qkv = rnd(b, n, 3 * heads * d, seed=77, dtype=dtype)
-    q, k = qkv[..., : heads * d], qkv[..., heads * d: 2 * heads * d]
-    k[0, 300] = (q[0, 5] * 6).to(dtype)          # key 300 (tile 4) aligned with query 5: a score far above its running maximum
-    k[0, 450] = (q[0, 130] * 8).to(dtype)
-    k[0, :64] = (k[0, :64] - 4 * q[0, 200:201]).to(dtype)   # first tile strongly negative for query 200
+    qkv = AR.maximum_jumps_late_qkv(dtype).cuda()
     out = torch.empty(b, n, heads * d, dtype=dtype, device="cuda")
     capi.check(lib.etainv_op_self_attention(capi.ptr(qkv), capi.ptr(out), b, n, heads, d, 0, 1, capi.dtype_code(dtype), capi.stream_ptr()))
     ref = ref_self_attention(qkv, heads)
     assert torch.isfinite(out).all()
+    AR.check_attention(out, ref, heads, d, dtype, 1.0, "maximum_jumps_late route=" + AR.self_attention_route(b, n, heads, d, n_cu()),
+                       emulate=lambda: AR.emulate_16bit(qkv, heads), query_ref=AR.ref_self_attention(AR.prescale_q(qkv, heads, d), heads, prescaled=True))
     assert relerr(out, ref) < TOL[dtype]
     assert relerr(out[0, [5, 130, 200]], ref[0, [5, 130, 200]]) < 2 * TOL[dtype]
 
@@ -899,7 +899,7 @@ def test_self_attention_d40_single_row_call_equals_the_row_of_a_batch(capi, dtyp
     one_in, one = qkv[3:4].contiguous(), torch.empty(1, n, heads * d, dtype=dtype, device="cuda")
     capi.check(lib.etainv_op_self_attention(capi.ptr(one_in), capi.ptr(one), 1, n, heads, d, 0, 1, capi.dtype_code(dtype), capi.stream_ptr()))
     assert torch.equal(one[0], out[3])
-    assert relerr(one, ref_self_attention(one_in, heads)) < TOL[dtype]
+    _check(one, one_in, heads, d, label="single_row")
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -908,22 +908,11 @@ def test_self_attention_d40_speculative_maximum(capi, dtype):
     non-finite repeats its pass with the running maximum (attention.hip, self_attn40_kernel).  N = 2048 (32 tiles), four regimes in ONE launch, each in its own
     (batch row, head) so that blocks of both kinds run side by side:  row 0 plain;  row 1: late keys 2^6 .. 2^12 above the first tile's maximum for some queries
     (the tracked pass would move m', the speculative one keeps P large: no overflow in either dtype);  row 2: one late key ~2^40 above it (fp16 P overflows ->
-    fallback; bf16 stays finite);  row 3: the first tile far BELOW everything else for every query (all of P large)."""
+    fallback; bf16 stays finite);  row 3: the first tile far BELOW everything else for every query (all of P large).
+    The per-item bounds (x 1.5 like the per-row bound) hold on every row: the emulation stays below half of them on these inputs too (test_attention_ref.py)."""
     lib = capi.load()
     b, heads, n, d = 4, 8, 2048, 40
-    qkv = rnd(b, n, 3 * heads * d, seed=123, dtype=dtype)
-    q, k = qkv[..., : heads * d], qkv[..., heads * d: 2 * heads * d]
-    sc = 1.0 / (d ** 0.5)
-    def boost(row, head, key, query, log2_gain):
-        # make score(query, key) of (row, head) ~ log2_gain * ln 2 above that query's typical maximum: k := q * t with t = gain / (|q|^2 * scale)
-        qv = q[row, query, head * d:(head + 1) * d].float()
-        t = (log2_gain * 0.6931 + 6.0) / (float(qv @ qv) * sc)
-        k[row, key, head * d:(head + 1) * d] = (qv * t).to(dtype)
-    for i, (key, g) in enumerate([(700, 6), (1300, 9), (2000, 12), (1999, 8)]):
-        boost(1, i % heads, key, 64 * i + 7, g)
-    boost(2, 3, 1500, 300, 40)
-    k[3, :64] = (k[3, :64] * 0.02).to(dtype)
-    q[3] = (q[3] * 3).to(dtype)                      # sharper rows: the first tile's maximum sits well below the later tiles'
+    qkv = AR.speculative_maximum_qkv(b, heads, n, d, dtype, 123, AR.SPECULATIVE_ITEMS).cuda()
     out = torch.empty(b, n, heads * d, dtype=dtype, device="cuda")
     capi.check(lib.etainv_op_self_attention(capi.ptr(qkv), capi.ptr(out), b, n, heads, d, 0, 1, capi.dtype_code(dtype), capi.stream_ptr()))
     ref = ref_self_attention(qkv, heads)
@@ -931,6 +920,7 @@ def test_self_attention_d40_speculative_maximum(capi, dtype):
     for row in range(b):
         assert relerr(out[row], ref[row]) < 1.5 * TOL[dtype], row
     assert relerr(out[2, 300, 3 * d:4 * d], ref[2, 300, 3 * d:4 * d]) < 2 * TOL[dtype]     # the query whose key forced the fallback pass in fp16
+    _check(out, qkv, heads, d, factor=1.5, label="speculative_maximum")
 
 
 def _self40(capi, qkv, b, n, heads, mode=0, n_img=1, d=40):
@@ -950,9 +940,7 @@ def test_self_attention_d40_persistent_kernel(capi, dtype, n, b, heads, monkeypa
     out = _self40(capi, qkv, b, n, heads)
     monkeypatch.setenv("ETAINV_A40_PERSIST", "0")
     old = _self40(capi, qkv, b, n, heads)
-    ref = ref_self_attention(qkv, heads)
-    assert torch.isfinite(out).all()
-    assert relerr(out, ref) < TOL[dtype]
+    ref = _check(out, qkv, heads, 40, label="persistent40")
     assert abs(relerr(out, ref) - relerr(old, ref)) < 0.1 * TOL[dtype]       # the same precision as the kernel it replaces ...
     assert not torch.equal(out, old) or n < 1024                               # ... which is another kernel (the switch works)
 
@@ -967,17 +955,7 @@ def test_self_attention_d80_persistent_kernel(capi, dtype, n, b, heads, mode, mo
     out = _self40(capi, qkv, b, n, heads, mode, n_img, d)
     monkeypatch.setenv("ETAINV_A80_PERSIST", "0")
     old = _self40(capi, qkv, b, n, heads, mode, n_img, d)
-    ident = torch.arange(b)
-    qm, km, vm = ident.clone(), ident.clone(), ident.clone()
-    for img in range(n_img if mode else 0):
-        u_s, u_t, c_s, c_t = img, n_img + img, 2 * n_img + img, 3 * n_img + img
-        if mode == 1:
-            qm[c_t], km[c_t] = c_s, c_s
-        else:
-            km[u_t], vm[u_t], km[c_t], vm[c_t] = u_s, u_s, c_s, c_s
-    ref = ref_self_attention(qkv, heads, qm, km, vm)
-    assert torch.isfinite(out).all()
-    assert relerr(out, ref) < TOL[dtype]
+    ref = _check(out, qkv, heads, d, AR.row_maps(b, n_img, mode, 0), label=f"persistent80 mode={mode}")
     assert abs(relerr(out, ref) - relerr(old, ref)) < 0.1 * TOL[dtype]
     assert not torch.equal(out, old)
 
@@ -985,28 +963,18 @@ def test_self_attention_d80_persistent_kernel(capi, dtype, n, b, heads, mode, mo
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_self_attention_d40_persistent_kernel_exact_pass(capi, dtype):
     """The four regimes of test_self_attention_d40_speculative_maximum inside a 16-row launch of the persistent kernel: an item whose denominators overflow (fp16,
-    row 2) is repeated with the running maximum INSIDE the item loop, and the block then restarts its K / V stream for the next item."""
+    row 2) is repeated with the running maximum INSIDE the item loop, and the block then restarts its K / V stream for the next item.
+    fp16: three items (first, middle, last query block) take the exact pass."""
     b, heads, n, d = 16, 8, 2048, 40
-    qkv = rnd(b, n, 3 * heads * d, seed=321, dtype=dtype)
-    q, k = qkv[..., : heads * d], qkv[..., heads * d: 2 * heads * d]
-    sc = 1.0 / (d ** 0.5)
-    def boost(row, head, key, query, log2_gain):
-        qv = q[row, query, head * d:(head + 1) * d].float()
-        t = (log2_gain * 0.6931 + 6.0) / (float(qv @ qv) * sc)
-        k[row, key, head * d:(head + 1) * d] = (qv * t).to(dtype)
-    for i, (key, g) in enumerate([(700, 6), (1300, 9), (2000, 12), (1999, 8)]):
-        boost(1, i % heads, key, 64 * i + 7, g)
-    for row, head, key, query in [(2, 3, 1500, 300), (7, 0, 100, 1999), (15, 7, 2047, 0)]:   # fp16: three items (first, middle, last query block) take the exact pass
-        boost(row, head, key, query, 40)
-    k[3, :64] = (k[3, :64] * 0.02).to(dtype)
-    q[3] = (q[3] * 3).to(dtype)
+    qkv = AR.speculative_maximum_qkv(b, heads, n, d, dtype, 321, AR.EXACT_PASS_ITEMS).cuda()
     out = _self40(capi, qkv, b, n, heads)
     ref = ref_self_attention(qkv, heads)
     assert torch.isfinite(out).all()
     for row in range(b):
         assert relerr(out[row], ref[row]) < 1.5 * TOL[dtype], row
-    for row, head, query in [(2, 3, 300), (7, 0, 1999), (15, 7, 0)]:
+    for row, head, _, query in AR.EXACT_PASS_ITEMS:
         assert relerr(out[row, query, head * d:(head + 1) * d], ref[row, query, head * d:(head + 1) * d]) < 2 * TOL[dtype], (row, head, query)
+    _check(out, qkv, heads, d, factor=1.5, label="exact_pass")
 
 
 @pytest.mark.parametrize("mode", [1, 2])
@@ -1017,15 +985,7 @@ def test_self_attention_d40_persistent_kernel_remaps(capi, mode, dtype):
     b = 4 * n_img
     qkv = rnd(b, n, 3 * heads * 40, seed=5 + mode, dtype=dtype)
     out = _self40(capi, qkv, b, n, heads, mode, n_img)
-    ident = torch.arange(b)
-    qm, km, vm = ident.clone(), ident.clone(), ident.clone()
-    for img in range(n_img):
-        u_s, u_t, c_s, c_t = img, n_img + img, 2 * n_img + img, 3 * n_img + img
-        if mode == 1:
-            qm[c_t], km[c_t] = c_s, c_s
-        else:
-            km[u_t], vm[u_t], km[c_t], vm[c_t] = u_s, u_s, c_s, c_s
-    assert relerr(out, ref_self_attention(qkv, heads, qm, km, vm)) < TOL[dtype]
+    _check(out, qkv, heads, 40, AR.row_maps(b, n_img, mode, 0), label=f"persistent40 mode={mode}")
 
 
 @pytest.mark.parametrize("mode", [1, 2])
@@ -1037,17 +997,7 @@ def test_self_attention_d40_remaps(capi, mode, dtype):
     qkv = rnd(b, n, 3 * heads * d, seed=3, dtype=dtype)
     out = torch.empty(b, n, heads * d, dtype=dtype, device="cuda")
     capi.check(lib.etainv_op_self_attention(capi.ptr(qkv), capi.ptr(out), b, n, heads, d, mode, n_img, capi.dtype_code(dtype), capi.stream_ptr()))
-    ident = torch.arange(b)
-    qm, km, vm = ident.clone(), ident.clone(), ident.clone()
-    for img in range(n_img):
-        u_s, u_t, c_s, c_t = img, n_img + img, 2 * n_img + img, 3 * n_img + img
-        if mode == 1:
-            qm[c_t] = c_s
-            km[c_t] = c_s
-        else:
-            km[u_t], vm[u_t] = u_s, u_s
-            km[c_t], vm[c_t] = c_s, c_s
-    assert relerr(out, ref_self_attention(qkv, heads, qm, km, vm)) < TOL[dtype]
+    _check(out, qkv, heads, d, AR.row_maps(b, n_img, mode, 0), label=f"d40 mode={mode}")
 
 
 @pytest.mark.parametrize("mode", [1, 2])
@@ -1059,17 +1009,7 @@ def test_self_attention_remaps(capi, mode):
     qkv = rnd(b, n, 3 * heads * d, seed=2, dtype=dtype)
     out = torch.empty(b, n, heads * d, dtype=dtype, device="cuda")
     capi.check(lib.etainv_op_self_attention(capi.ptr(qkv), capi.ptr(out), b, n, heads, d, mode, n_img, capi.F16, capi.stream_ptr()))
-    ident = torch.arange(b)
-    qm, km, vm = ident.clone(), ident.clone(), ident.clone()
-    for img in range(n_img):
-        u_s, u_t, c_s, c_t = img, n_img + img, 2 * n_img + img, 3 * n_img + img
-        if mode == 1:
-            qm[c_t] = c_s
-            km[c_t] = c_s
-        else:
-            km[u_t], vm[u_t] = u_s, u_s
-            km[c_t], vm[c_t] = c_s, c_s
-    assert relerr(out, ref_self_attention(qkv, heads, qm, km, vm)) < TOL[dtype]
+    _check(out, qkv, heads, d, AR.row_maps(b, n_img, mode, 0), label=f"d80 mode={mode}")
 
 
 def test_masactrl_vs_reference_golden(capi, golden):
@@ -1106,10 +1046,11 @@ def _ptp_tables(n_img):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("n,d", [(256, 160), (1024, 80), (4096, 40), (64, 160)])
+@pytest.mark.parametrize("n,d", [(256, 160), (1024, 80), (4096, 40), (64, 160), (9216, 40), (2304, 80), (576, 160), (144, 160)])
 def test_cross_attention_ptp_edit_and_store(capi, dtype, n, d):
     """Cross-attention with the fused Refine + Reweight edit on the cond target rows and AttentionStore accumulation,
-    against the oracle's controller algebra (pinned by tests/golden/ptp_algebra.npz) on materialised probabilities."""
+    against the oracle's controller algebra (pinned by tests/golden/ptp_algebra.npz) on materialised probabilities.  Token counts of the 512^2 and 768^2
+    configurations; the bound holds per (row, head, 32-query block) as well as globally."""
     from oracle import ptp as optp
     lib = capi.load()
     n_img, heads = 2, 8
@@ -1142,6 +1083,9 @@ def test_cross_attention_ptp_edit_and_store(capi, dtype, n, d):
         ref_maps[img, 1] = probs[rows[3]]
     ref = (probs.cuda() @ sp(v, 77)).permute(0, 2, 1, 3).reshape(b, n, c)
     assert relerr(out, ref) < TOL[dtype]
+    _, blk, _, where = AR.attn_errors(out, ref, heads, d)
+    print(f"cross-attention n={n} d={d} {dtype}: global {relerr(out, ref):.3e} worst (row, head, 32-query block) {blk:.3e} / {TOL[dtype]:.1e}")
+    assert blk < TOL[dtype], where["block"]
     if store:
         assert relerr(maps[3].cpu(), 2 * ref_maps) < 1e-3
         assert float(maps[0].abs().max()) == 0.0
