@@ -1,6 +1,6 @@
 // Attention kernels for the SD1.x transformer blocks (heads = 8, head_dim 40 / 80 / 160).
 //
-// self_attn_kernel : flash-style softmax(Q K^T * scale) V over N = 64 .. 9216 tokens.  The N x N probability
+// self_attn40_kernel / self_attn40q_kernel: flash-style softmax(Q K^T * scale) V over N = 64 .. 9216 tokens.  The N x N probability
 //   matrix the reference materialises for its hooks (ptp_utils.py:238-253: 2.9 GB of traffic per sample
 //   forward) never exists; the prompt-to-prompt self-replace (ptp.py:194-199: target probs := source probs,
 //   i.e. softmax(Q_s K_s^T) V_t) and MasaCtrl (masactrl.py:56-72: K, V of the source sample) are expressed as
@@ -9,7 +9,7 @@
 //   (Refine ptp.py:245-251, Reweight :261-268, time blend :212-214) and the AttentionStore accumulation of
 //   the (L/4)^2-token layers (ptp.py:150-167) into the softmax epilogue.
 //
-// MFMA orientation (both kernels): S^T = K Q^T and O^T = V^T P^T with v_mfma_f32_16x16x32, so the QUERY
+// MFMA orientation: S^T = K Q^T and O^T = V^T P^T (cross_attn_kernel: v_mfma_f32_16x16x32; the self kernels: 32x32x16, see there), so the QUERY
 // index lives on lane&15 for scores, probabilities and output alike: row max / sum are 2 shuffles, the
 // online-softmax rescale is lane-local, and the S^T accumulator registers are already the B operand of the
 // PV product (keys of a 32-key step are taken in the order the accumulators hold them; V^T is read in that
@@ -19,6 +19,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "self_attn_route.h"
 
 namespace etainv {
 
@@ -35,31 +36,6 @@ template <> struct Frag<bf16> {
 };
 
 constexpr float NEG_BIG = -1.0e30f;
-// Measured A/B switches (MI355X, N = 4096, d = 40, 128 rows; same device, same call): packed-FMA / v_max3 softmax 4.66 ms;
-// + literal-zero first MFMA 4.66; + lazy running max (wave-uniform branch) 4.93; + bounds-free K/V load variant 5.20.
-// The branchy variants lose more to the split basic blocks than the skipped instructions save: all off.
-#ifndef ATT_ZERO_LITERAL
-#define ATT_ZERO_LITERAL 0
-#endif
-#ifndef ATT_LOAD_SPLIT
-#define ATT_LOAD_SPLIT 0
-#endif
-#ifndef ATT_LAZY
-#define ATT_LAZY 0
-#endif
-#ifndef ATT_ABL
-#define ATT_ABL 0   // timing-only ablations of self_attn40_kernel (bit 0: no running maximum, 1: no exponentials, 2: no barrier, 3: no V fragment reads, 4: no K fragment reads): never in a product build
-#endif
-#ifndef ATT_SPEC_MAX
-#define ATT_SPEC_MAX 1   // A/B: 0 = the running maximum in every tile (rounds 2-5)
-#endif
-#ifndef ETAINV_QT40
-#define ETAINV_QT40 4
-#endif
-#ifndef ETAINV_QT80
-#define ETAINV_QT80 2
-#endif
-constexpr int SELF_QT(int d) { return d == 40 ? ETAINV_QT40 : d == 80 ? ETAINV_QT80 : 2; }
 
 // batch-row roles for the backward layout [u_s x B, u_t x B, c_s x B, c_t x B]
 __device__ __forceinline__ void row_roles(int b, int n_img, int& half, int& role, int& img) {
@@ -68,283 +44,10 @@ __device__ __forceinline__ void row_roles(int b, int n_img, int& half, int& role
   img = b % n_img;
 }
 
-// ------------------------------------------------------------------------------------------------ self
-// mode: 0 plain; 1 ptp self-replace (cond target rows take Q,K of their source row); 2 masactrl (target rows
-// of both halves take K,V of their source row)
-template <typename T, int D, int QT>
-__global__ void __launch_bounds__(256) self_attn_kernel(const T* __restrict__ qkv, T* __restrict__ out, int N, int heads,
-                                                        float scale_log2, int mode, int n_img, int stagger, int first_row) {
-  typedef typename Frag<T>::v8 v8;
-  typedef typename Frag<T>::v4 v4;
-  constexpr int DP = (D + 31) / 32 * 32;
-  constexpr int KS = DP / 32;
-  constexpr int DT = (D + 15) / 16;
-  constexpr int NCH = D / 8;
-  constexpr int KV = 64;
-  constexpr int KSTR = DP + 8;
-  constexpr int VSTR = KV + 8;
-  constexpr int NLD = (KV * NCH + 255) / 256;
-  constexpr int KBUF = KV * KSTR, VBUF = DT * 16 * VSTR;
-  // When D is not a multiple of 16 the padded V^T rows are free MFMA work: row D is all ones, so O^T row D = sum_k p
-  // (the softmax denominator, rescaled with the same alpha as O) and the per-element VALU add disappears.
-  constexpr bool ONES_ROW = (DT * 16 > D);
-
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  T* sK = reinterpret_cast<T*>(smem);      // [2][KV][KSTR]
-  T* sVt = sK + 2 * KBUF;                  // [2][DT*16][VSTR]
-
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int fr = lane & 15, q4 = lane >> 4;
-  const int b = blockIdx.z, h = blockIdx.y;
-  const int C = heads * D, C3 = 3 * C;
-  int bq = b, bk = b, bv = b;
-  if (mode != 0) {
-    int half, role, img;
-    if (first_row < 0) {   // rows [u_t, c_t, c_s] x n_img (etainv_attn_ctrl.src_exit_block): the cond target rows take Q, K of the cond source rows BEHIND them
-      if (mode == 1 && b / n_img == 1) { bq = b + n_img; bk = b + n_img; }
-    } else {
-      row_roles(b + first_row, n_img, half, role, img);   // (first_row: the call carries rows [first_row, 4 n_img) of the [u_s,u_t,c_s,c_t] layout)
-      if (mode == 1 && half == 1 && role == 1) { bq = b - n_img; bk = b - n_img; }
-      if (mode == 2 && role == 1) { bk = b - n_img; bv = b - n_img; }
-    }
-  }
-  const int q_base = blockIdx.x * (64 * QT) + wid * (16 * QT);
-  // De-phase the two blocks that share a CU (one wave of each per SIMD): both run [QK^T MFMAs | softmax VALU | PV MFMAs] with the
-  // same period, and started together they stay together -- matrix pipe and VALU are then each idle half of the time.
-  // Blocks 256..511 of every 512 (the second resident block of each CU under round-robin dispatch) start half a tile late.
-  if (stagger > 0) {
-    const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    if ((lin >> 8) & 1)
-      for (int i = 0; i < stagger; ++i) __builtin_amdgcn_s_sleep(1);
-  }
-
-  // one-time LDS init (both buffers): zero K padding columns (0 * garbage could be NaN), V^T padding rows (ones row)
-  if (DP > D) {
-    constexpr int PCH = (DP - D) / 8;
-    for (int idx = tid; idx < 2 * KV * PCH; idx += 256) {
-      const int bufi = idx / (KV * PCH), r = idx % (KV * PCH);
-      const int key = r / PCH, ch = r % PCH;
-      *reinterpret_cast<u32x4*>(sK + bufi * KBUF + key * KSTR + D + ch * 8) = (u32x4){0u, 0u, 0u, 0u};
-    }
-  }
-  if (ONES_ROW) {
-    for (int idx = tid; idx < 2 * (DT * 16 - D) * KV; idx += 256) {
-      const int bufi = idx / ((DT * 16 - D) * KV), r = idx % ((DT * 16 - D) * KV);
-      const int row = D + r / KV, key = r % KV;
-      sVt[bufi * VBUF + row * VSTR + key] = (T)(row == D ? 1.0f : 0.0f);
-    }
-  }
-
-  // Q fragments (B operand of S^T): lane holds Q[query fr][d = ks*32 + q4*8 .. +7]
-  v8 qf[QT][KS];
-#pragma unroll
-  for (int qt = 0; qt < QT; ++qt) {
-    int query = q_base + qt * 16 + fr;
-    query = query < N ? query : N - 1;
-    const T* qp = qkv + ((int64_t)bq * N + query) * C3 + h * D;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const int d0 = ks * 32 + q4 * 8;
-      u32x4 v = {0u, 0u, 0u, 0u};
-      if (d0 < D) v = *reinterpret_cast<const u32x4*>(qp + d0);
-      qf[qt][ks] = *reinterpret_cast<v8*>(&v);
-    }
-  }
-
-  u32x4 rk[NLD], rv[NLD];
-  const T* kbase = qkv + (int64_t)bk * N * C3 + C + h * D;
-  const T* vbase = qkv + (int64_t)bv * N * C3 + 2 * C + h * D;
-  auto load_kv = [&](int kv0, auto full_tag) {
-    constexpr bool FULL = ATT_LOAD_SPLIT && decltype(full_tag)::value;   // every key of the tile exists: no bounds test, no zero fill
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int idx = tid + 256 * i;
-      if (FULL) {
-        if (idx < KV * NCH) {   // (lanes past the last chunk never store their registers)
-          rk[i] = *reinterpret_cast<const u32x4*>(kbase + (int64_t)(kv0 + idx / NCH) * C3 + (idx % NCH) * 8);
-          rv[i] = *reinterpret_cast<const u32x4*>(vbase + (int64_t)(kv0 + idx % KV) * C3 + (idx / KV) * 8);
-        }
-      } else {
-        u32x4 a = {0u, 0u, 0u, 0u}, c = {0u, 0u, 0u, 0u};
-        if (idx < KV * NCH) {
-          {
-            const int key = idx / NCH, ch = idx % NCH;
-            if (kv0 + key < N) a = *reinterpret_cast<const u32x4*>(kbase + (int64_t)(kv0 + key) * C3 + ch * 8);
-          }
-          {
-            const int key = idx % KV, ch = idx / KV;
-            if (kv0 + key < N) c = *reinterpret_cast<const u32x4*>(vbase + (int64_t)(kv0 + key) * C3 + ch * 8);
-          }
-        }
-        rk[i] = a;
-        rv[i] = c;
-      }
-    }
-  };
-  auto store_kv = [&](int bufi) {
-    T* dK = sK + bufi * KBUF;
-    T* dV = sVt + bufi * VBUF;
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int idx = tid + 256 * i;
-      if (idx < KV * NCH) {
-        {
-          const int key = idx / NCH, ch = idx % NCH;
-          *reinterpret_cast<u32x4*>(dK + key * KSTR + ch * 8) = rk[i];
-        }
-        {
-          const int key = idx % KV, ch = idx / KV;
-          const T* e = reinterpret_cast<const T*>(&rv[i]);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) dV[(ch * 8 + j) * VSTR + key] = e[j];
-        }
-      }
-    }
-  };
-
-  // running max of the RAW scores (scale folded into the exponent: p = exp2(s*c - m*c), one FMA + one v_exp per element)
-  float m_run[QT], l_run[QT];
-  f32x4 acc[QT][DT];
-#pragma unroll
-  for (int qt = 0; qt < QT; ++qt) {
-    m_run[qt] = NEG_BIG;
-    l_run[qt] = 0.f;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) acc[qt][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  }
-
-  const int ntiles = (N + KV - 1) / KV;
-  const int nfull = N / KV;
-  if (KV <= N) load_kv(0, std::true_type{});
-  else load_kv(0, std::false_type{});
-  store_kv(0);
-  __syncthreads();
-
-  auto tile_body = [&](int j, auto ragged_tag) {
-    constexpr bool RAGGED = decltype(ragged_tag)::value;
-    const int kv0 = j * KV, cur = j & 1;
-    if (j + 1 < nfull) load_kv(kv0 + KV, std::true_type{});
-    else if (j + 1 < ntiles) load_kv(kv0 + KV, std::false_type{});
-    const T* tK = sK + cur * KBUF;
-    const T* tV = sVt + cur * VBUF;
-
-    // ---- S^T = K Q^T : s[qt][kt] holds keys kt*16 + q4*4 + r for query fr
-    f32x4 s[QT][4];
-#if !ATT_ZERO_LITERAL
-#pragma unroll
-    for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt) s[qt][kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#endif
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt) {
-        v8 kf = *reinterpret_cast<const v8*>(tK + (kt * 16 + fr) * KSTR + ks * 32 + q4 * 8);
-        // first K step: C = literal 0 (an inline-constant MFMA operand; zeroing 64 accumulator registers per tile was 6 % of
-        // the loop's issue slots)
-#pragma unroll
-        for (int qt = 0; qt < QT; ++qt) s[qt][kt] = Frag<T>::mfma(kf, qf[qt][ks], (ATT_ZERO_LITERAL && ks == 0) ? (f32x4){0.f, 0.f, 0.f, 0.f} : s[qt][kt]);
-      }
-    if constexpr (RAGGED) {   // only the last tile of a sequence that is not a multiple of 64 keys
-#pragma unroll
-      for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (kv0 + kt * 16 + q4 * 4 + r >= N) s[qt][kt][r] = NEG_BIG;
-    }
-
-    // ---- online softmax per query (lane-local + 2 shuffles), P packed straight into PV operands.
-    // VALU ops and MFMA issue share the SIMD's vector issue port (PMC: 40 % of wave cycles issuing, 79 % of that VALU), so the
-    // softmax is written for instruction count: v_max3 chains and packed-fp32 FMAs for the exponent arguments.  (ATT_LAZY: the
-    // stored max only moves when a query would exceed it by 2^6 -- fewer instructions, but slower, see the switches above.)
-    v8 pf[QT][2];
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-    for (int qt = 0; qt < QT; ++qt) {
-      float mx = fmaxf(fmaxf(s[qt][0][0], s[qt][0][1]), s[qt][0][2]);
-      mx = fmaxf(fmaxf(mx, s[qt][0][3]), s[qt][1][0]);
-#pragma unroll
-      for (int e = 5; e + 1 < 16; e += 2) mx = fmaxf(fmaxf(mx, s[qt][e >> 2][e & 3]), s[qt][(e + 1) >> 2][(e + 1) & 3]);
-      mx = fmaxf(mx, s[qt][3][3]);
-      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      if (!ATT_LAZY || __builtin_amdgcn_ballot_w64((mx - m_run[qt]) * scale_log2 > 6.0f) != 0) {
-        const float m_new = fmaxf(m_run[qt], mx);
-        const float alpha = __builtin_amdgcn_exp2f((m_run[qt] - m_new) * scale_log2);
-        m_run[qt] = m_new;
-        if (!ONES_ROW) l_run[qt] *= alpha;
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) acc[qt][dt] *= alpha;
-      }
-      const float nm = -m_run[qt] * scale_log2;
-      const f32x2 sc2 = {scale_log2, scale_log2}, nm2 = {nm, nm};
-      float rs = 0.f;
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; r += 2) {
-          const f32x2 t = (f32x2){s[qt][kt][r], s[qt][kt][r + 1]} * sc2 + nm2;
-          const float p0 = __builtin_amdgcn_exp2f(t[0]), p1 = __builtin_amdgcn_exp2f(t[1]);
-          if (!ONES_ROW) rs += p0 + p1;
-          pf[qt][kt >> 1][(kt & 1) * 4 + r] = (T)p0;
-          pf[qt][kt >> 1][(kt & 1) * 4 + r + 1] = (T)p1;
-        }
-      if (!ONES_ROW) l_run[qt] += rs;
-    }
-
-    // ---- O^T += V^T P^T
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        const T* vp = tV + (dt * 16 + fr) * VSTR + ks * 32 + q4 * 4;
-        v4 lo = *reinterpret_cast<const v4*>(vp);
-        v4 hi = *reinterpret_cast<const v4*>(vp + 16);
-        v8 vf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-#pragma unroll
-        for (int qt = 0; qt < QT; ++qt) acc[qt][dt] = Frag<T>::mfma(vf, pf[qt][ks], acc[qt][dt]);
-      }
-
-    if (j + 1 < ntiles) store_kv(cur ^ 1);   // buffer cur^1 was last read in iteration j-1, a barrier ago
-    __syncthreads();
-  };
-  for (int j = 0; j < nfull; ++j) tile_body(j, std::false_type{});
-  if (nfull < ntiles) tile_body(nfull, std::true_type{});
-
-  // ---- normalise and store: lane holds channels dt*16 + q4*4 + r of query fr
-#pragma unroll
-  for (int qt = 0; qt < QT; ++qt) {
-    float l;
-    if (ONES_ROW) {
-      // denominator = O^T row D: tile DT-1, lane group q4 = (D % 16) / 4, register (D % 4) == 0
-      l = __shfl(acc[qt][DT - 1][D % 4], fr + 16 * ((D % 16) / 4), 64);
-    } else {
-      l = l_run[qt];
-      l += __shfl_xor(l, 16, 64);
-      l += __shfl_xor(l, 32, 64);
-    }
-    const float inv = 1.f / l;
-    const int query = q_base + qt * 16 + fr;
-    if (query >= N) continue;
-    T* op = out + ((int64_t)b * N + query) * C + h * D;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) {
-      const int dc = dt * 16 + q4 * 4;
-      if (dc < D) {
-        T o[4] = {(T)(acc[qt][dt][0] * inv), (T)(acc[qt][dt][1] * inv), (T)(acc[qt][dt][2] * inv), (T)(acc[qt][dt][3] * inv)};
-        *reinterpret_cast<u32x2*>(op + dc) = *reinterpret_cast<u32x2*>(o);
-      }
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------------------------ self, head_dim 40 (v2)
 // The 64^2- and 96^2-token levels (N = 4096 / 9216, d = 40) are 85 % of the self-attention FLOPs of the UNet and ran at 23 % of the MFMA
-// peak in the generic kernel above: the loop is bound by the SIMD's vector-issue port (PMC: 40 % of wave cycles issuing, 79 % of that
-// VALU), with one v_exp_f32 (8 issue cycles) per 160 FLOPs.  This kernel removes everything else from the per-element path:
+// peak in the round-1 generic 16x16x32 kernel (retired: tools/experiments/attention_r06/README.md): the loop was bound by the SIMD's vector-issue port
+// (PMC: 40 % of wave cycles issuing, 79 % of that VALU), with one v_exp_f32 (8 issue cycles) per 160 FLOPs.  This kernel removes everything else from the per-element path:
 //   * v_mfma_f32_32x32x16 for both products: an MFMA holds the issue port 8 of its 32 cycles (16x16x32: 8 of 16), and K = 16 steps pad
 //     40 -> 48 (not 64) in S^T = K Q^T.  Query on lane & 31, the 16 accumulator registers of a 32-key block are directly the B operand
 //     of two K = 16 steps of O^T = V^T P^T (keys taken in the order the accumulator holds them: step s <- registers 8s .. 8s+7, i.e.
@@ -357,7 +60,7 @@ __global__ void __launch_bounds__(256) self_attn_kernel(const T* __restrict__ qk
 //     accumulate in fp32.  m' is kept representable in the operand type, so the value the MFMA subtracts and the value the rescale
 //     uses are the same number;
 //   * the softmax denominator is row 40 of O^T: the pad chunk of every V row is (1, 0, ...), the MFMA sums p for free;
-//   * V stays row-major [key][48] in LDS (16-byte staging stores, no 2-byte transposition: 39 % of the LDS cycles of the generic kernel
+//   * V stays row-major [key][48] in LDS (16-byte staging stores, no 2-byte transposition: 39 % of the LDS cycles of that generic kernel
 //     were bank conflicts of those stores) and is read transposed by ds_read_b64_tr_b16.
 // Per 64-key tile and 32-query block: 14 MFMAs (448 matrix cycles), 32 v_exp + 16 v_max3 + 16 v_cvt_pk (~400 issue cycles).
 template <typename T> struct Frag32;
@@ -378,11 +81,7 @@ template <int D> struct A32 {
   // V row in elements: D dims + pad chunk, rounded up to a stride of 64 bytes times an odd number -- the transposed reads of a 32-lane half
   // touch 64 bytes (two 16-dim groups) of 4 consecutive rows, and only such strides put those four segments on different banks (48 elements =
   // 96 bytes wrapped the fourth row onto the first: PMC 37 % of the kernel's LDS cycles were bank conflicts); 96 / 96
-#ifndef ETAINV_A40_VROW_PLAIN
   static constexpr int VROW = ((D + 8 + 31) / 32 | 1) * 32;
-#else
-  static constexpr int VROW = (D + 8 + 15) / 16 * 16;
-#endif
   static constexpr int DT = (D + 1 + 31) / 32;               // 32-row tiles of O^T incl. the denominator row D (2 / 3)
   static constexpr bool ZBUF = DT * 32 > VROW;               // V^T rows past VROW are read from an all-zero image (D = 40: rows 48 .. 63)
   static constexpr int KBUF = KV * KROW, VBUF = KV * VROW;
@@ -412,9 +111,11 @@ __device__ __forceinline__ float max32(const f32x16 (&s)[2]) {
   return fmaxf(fmaxf(m, c[3]), fmaxf(l, s[1][15]));
 }
 
+// mode: 0 plain; 1 ptp self-replace (cond target rows take Q,K of their source row); 2 masactrl (target rows
+// of both halves take K,V of their source row)
 template <typename T, int D, bool XCD_REMAP, int QB, int OCC>
 __global__ void __launch_bounds__(256, OCC) self_attn40_kernel(const T* __restrict__ qkv, T* __restrict__ out, int N, int heads,
-                                                               float q_scale, int mode, int n_img, int nqb, int stagger, int first_row, int hm_rows) {
+                                                               float q_scale, int mode, int n_img, int nqb, int first_row, int hm_rows) {
   // hm_rows > 0: qkv holds three head-major planes [q|k|v][hm_rows batch rows][head][token][D] (IGemmParams::hm_*): a 64-key tile is one contiguous block
   typedef typename Frag<T>::v8 v8;
   typedef A32<D> GEO;
@@ -455,10 +156,6 @@ __global__ void __launch_bounds__(256, OCC) self_attn40_kernel(const T* __restri
     }
   }
   const int q_base = qblk * (128 * QB) + wid * (32 * QB);
-  // experiment (ETAINV_A40_STAGGER, 64-cycle ticks): delay the second co-resident block of each CU (ids 256 .. 511 of every 512 under
-  // round-robin dispatch) so that its matrix phases meet the first block's softmax phases
-  if (stagger > 0 && ((blockIdx.x >> 8) & 1))
-    for (int i = 0; i < stagger; ++i) __builtin_amdgcn_s_sleep(1);
 
   // ---- one-time LDS constants: pad chunks (1, 0 x 7) of every K and V row of both buffers, the all-zero V image
   {
@@ -580,9 +277,6 @@ __global__ void __launch_bounds__(256, OCC) self_attn40_kernel(const T* __restri
           const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vp_));
           const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vp_ + 8 * VROW));
           vf[ks][dt] = __builtin_bit_cast(v8, (s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-#if ATT_ABL & 8   // timing only: no V fragment reads
-          vf[ks][dt] = qf[0][(ks + dt) % KS];
-#endif
         }
     };
 
@@ -593,9 +287,6 @@ __global__ void __launch_bounds__(256, OCC) self_attn40_kernel(const T* __restri
 #pragma unroll
       for (int st = 0; st < KS; ++st) {
         v8 kf = *reinterpret_cast<const v8*>(tK + kb * 32 * KROW + st * 16);
-#if ATT_ABL & 16   // timing only: no K fragment reads
-        kf = qf[QB - 1][(st + kb) % KS];
-#endif
 #pragma unroll
         for (int qb = 0; qb < QB; ++qb) {
           if (st == 0) {
@@ -621,9 +312,6 @@ __global__ void __launch_bounds__(256, OCC) self_attn40_kernel(const T* __restri
     // ---- reference maximum: moves only when a query exceeds it by 2^THR (or on the first tile)
     if (track || j == 0) {
     float mx[QB];
-#if ATT_ABL & 1
-    if (j == 0)
-#endif
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) {
       const float m = max32(s[qb]);
@@ -636,11 +324,7 @@ __global__ void __launch_bounds__(256, OCC) self_attn40_kernel(const T* __restri
       mx[qb] = fmaxf(ma, mb);   // both key halves of the query
     }
     const bool first = j == 0;
-#if ATT_ABL & 1   // timing only: no running maximum after the first tile
-    if (first) {
-#else
     if (first || __builtin_amdgcn_ballot_w64(fmaxf(mx[0], mx[QB - 1]) > A40_THR) != 0) {
-#endif
 #pragma unroll
       for (int qb = 0; qb < QB; ++qb) {
         const float d = first ? mx[qb] : fmaxf(mx[qb], 0.f);
@@ -676,11 +360,7 @@ __global__ void __launch_bounds__(256, OCC) self_attn40_kernel(const T* __restri
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
-#if ATT_ABL & 2   // timing only: no exponentials
-        for (int e = 0; e < 8; ++e) pf[qb][ks][e] = (T)(s[qb][ks >> 1][(ks & 1) * 8 + e]);
-#else
         for (int e = 0; e < 8; ++e) pf[qb][ks][e] = (T)__builtin_amdgcn_exp2f(s[qb][ks >> 1][(ks & 1) * 8 + e]);
-#endif
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
@@ -688,11 +368,7 @@ __global__ void __launch_bounds__(256, OCC) self_attn40_kernel(const T* __restri
     }
 
     if (j + 1 < ntiles) store_kv(cur ^ 1);   // buffer cur^1 was last read in iteration j-1, a barrier ago
-#if ATT_ABL & 4   // timing only: no barrier (races)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#else
     __syncthreads();
-#endif
   };
   // Pass 0 is speculative: only tile 0 computes its maximum (m' = the exact maximum of the first 64 keys); the later tiles skip the 34 v_max3 + swap + ballot +
   // branch per wave and tile (the round-6 ablation priced them at 7.5 % of the kernel: every instruction of this loop costs its issue time) and exponentiate
@@ -701,7 +377,7 @@ __global__ void __launch_bounds__(256, OCC) self_attn40_kernel(const T* __restri
   // the denominator row comes out non-finite, and the whole block repeats the pass with the running maximum of rounds 2-5 (pass 1): correct for every input,
   // twice the time on the blocks that need it (attention rows of SD1.x: none seen; the jump tests of tests/test_kernels_gpu.py take this path).  Where the
   // tracked pass would never have moved m', both passes are the same instructions on the same data.
-  for (int pass = (ATT_SPEC_MAX && ntiles >= 8) ? 0 : 1; pass < 2; ++pass) {   // (a few tiles: the tracked pass at once -- N = 256, d = 160: 0.132 vs 0.140 ms)
+  for (int pass = ntiles >= 8 ? 0 : 1; pass < 2; ++pass) {   // (a few tiles: the tracked pass at once -- N = 256, d = 160: 0.132 vs 0.140 ms)
     track = pass == 1;
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) {
@@ -760,7 +436,7 @@ __global__ void __launch_bounds__(256, OCC) self_attn40_kernel(const T* __restri
 // Measured (same box, N = 4096 x 128 rows / N = 9216 x 32 rows): 3.06 / 3.53 ms against 3.18-3.20 / 3.74 for self_attn40_kernel; the tile loop runs 2670 cycles per tile against an
 // in-order issue sum of ~2400 (128 v_exp_f32 = 1250 of it).  QB = 2 with eight waves (NW = 8: same code, 256 registers, 13 spilled): 3.10 ms, not dispatched.
 // head_dim 80 (the (L/2)^2 level; 24 MFMAs per unit, matrix-bound) runs the same code with QB = 2, NW = 4 and items of 256 queries: 0.443 against 0.491 ms at N = 1024 x 128 rows.
-// Requirements (persistent_self_ok): N a multiple of the item's queries and of 256 (tiles: a multiple of 4, >= 16), the QKV tensor below 4 GB (one buffer descriptor, 32-bit
+// Requirements (persistent_self_ok, self_attn_route.h): N a multiple of the item's queries and of 256 (tiles: a multiple of 4, >= 16), the QKV tensor below 4 GB (one buffer descriptor, 32-bit
 // scalar offsets), >= 2 items per CU.  ETAINV_A40_PERSIST=0 / ETAINV_A80_PERSIST=0: self_attn40_kernel as before.
 template <typename T, int D, int QB, int NW>
 __global__ void __launch_bounds__(64 * NW, 1) self_attn40q_kernel(const T* __restrict__ qkv, T* __restrict__ out, int N, int heads, float q_scale, int mode, int n_img,
@@ -1423,53 +1099,22 @@ __global__ void __launch_bounds__(256) cross_attn_kernel(const T* __restrict__ q
   }
 }
 
-template <typename T, int D>
-static int launch_self_t(const void* qkv, void* out, int b, int n, int heads, int mode, int n_img, hipStream_t s, int q_prescaled = 0, int first_row = 0) {
-  constexpr int QT = SELF_QT(D);
-  constexpr int DP = (D + 31) / 32 * 32, DT = (D + 15) / 16;
-  const size_t lds = (size_t)2 * (64 * (DP + 8) + DT * 16 * (64 + 8)) * sizeof(T);
-  static bool attr[kMaxDevices] = {};   // per device
-  const int dev = current_device();
-  if (!attr[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&self_attn_kernel<T, D, QT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr[dev] = true;
-  }
-  const float scale_log2 = q_prescaled ? 1.0f : (1.0f / sqrtf((float)D)) * 1.4426950408889634f;
-  ProfScope prof(PROF_SELF_ATTN, 4.0 * (double)b * heads * (double)n * (double)n * D, s);
-  static const int stagger = getenv("ETAINV_ATT_STAGGER") ? atoi(getenv("ETAINV_ATT_STAGGER")) : 0;
-  hipLaunchKernelGGL((self_attn_kernel<T, D, QT>), dim3(cdiv(n, 64 * QT), heads, b), dim3(256), lds, s, (const T*)qkv, (T*)out, n,
-                     heads, scale_log2, mode, n_img, stagger, first_row);
-  ETAINV_LAUNCH_CHECK();
-  return 0;
-}
-
-bool self_attn40_v2_enabled() {
-  static const bool on = !env_on("ETAINV_ATT_OLD");
-  return on;
-}
-
 template <typename T, int D, int QB, int OCC>
 static int launch_self40(const void* qkv, void* out, int b, int n, int heads, int mode, int n_img, int q_prescaled, hipStream_t s, int first_row = 0, int head_major = 0) {
   const int hm_rows = head_major ? b : 0;
   const int nqb = cdiv(n, 128 * QB);
   const bool remap = ((b * heads) % 8) == 0;
   const float q_scale = q_prescaled ? 1.0f : (1.0f / sqrtf((float)D)) * 1.4426950408889634f;
-  constexpr size_t A40_LDS = A32<D>::LDS;
+  constexpr size_t lds = A32<D>::LDS;
   ProfScope prof(PROF_SELF_ATTN, 4.0 * (double)b * heads * (double)n * (double)n * D, s);
-  static const int stagger = getenv("ETAINV_A40_STAGGER") ? atoi(getenv("ETAINV_A40_STAGGER")) : 0;
-  static const size_t lds_pad = getenv("ETAINV_A40_LDSPAD") ? (size_t)atoi(getenv("ETAINV_A40_LDSPAD")) : 0;   // experiment: fewer resident blocks
-  const size_t lds = A40_LDS + lds_pad;
-  static bool attr_set[kMaxDevices] = {};   // per device and instantiation (T, D, QB, OCC); the LDSPAD experiment changes the size per process only
-  const int dev = current_device();
-  if ((lds_pad || lds > 64 * 1024) && !attr_set[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&self_attn40_kernel<T, D, true, QB, OCC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&self_attn40_kernel<T, D, false, QB, OCC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set[dev] = true;
+  if constexpr (lds > 64 * 1024) {   // head_dim 160: 102 KB
+    allow_dynamic_lds<&self_attn40_kernel<T, D, true, QB, OCC>>(lds);
+    allow_dynamic_lds<&self_attn40_kernel<T, D, false, QB, OCC>>(lds);
   }
   if (remap)
-    hipLaunchKernelGGL((self_attn40_kernel<T, D, true, QB, OCC>), dim3(nqb * heads * b), dim3(256), lds, s, (const T*)qkv, (T*)out, n, heads, q_scale, mode, n_img, nqb, stagger, first_row, hm_rows);
+    hipLaunchKernelGGL((self_attn40_kernel<T, D, true, QB, OCC>), dim3(nqb * heads * b), dim3(256), lds, s, (const T*)qkv, (T*)out, n, heads, q_scale, mode, n_img, nqb, first_row, hm_rows);
   else
-    hipLaunchKernelGGL((self_attn40_kernel<T, D, false, QB, OCC>), dim3(nqb, heads, b), dim3(256), lds, s, (const T*)qkv, (T*)out, n, heads, q_scale, mode, n_img, nqb, stagger, first_row, hm_rows);
+    hipLaunchKernelGGL((self_attn40_kernel<T, D, false, QB, OCC>), dim3(nqb, heads, b), dim3(256), lds, s, (const T*)qkv, (T*)out, n, heads, q_scale, mode, n_img, nqb, first_row, hm_rows);
   ETAINV_LAUNCH_CHECK();
   return 0;
 }
@@ -1483,12 +1128,7 @@ static int launch_self40q(const void* qkv, void* out, int b, int n, int heads, i
   const int remap = ((b * heads) % 8) == 0;
   const float q_scale = q_prescaled ? 1.0f : (1.0f / sqrtf((float)D)) * 1.4426950408889634f;
   constexpr size_t lds = (size_t)(4 * (A32<D>::KBUF + A32<D>::VBUF) + A32<D>::VBUF) * 2;   // four tile buffers + the zero image (90 / 112 KB at head_dim 40 / 80; one block per CU)
-  static bool attr_set[kMaxDevices] = {};
-  const int dev = current_device();
-  if (!attr_set[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&self_attn40q_kernel<T, D, QB, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set[dev] = true;
-  }
+  allow_dynamic_lds<&self_attn40q_kernel<T, D, QB, NW>>(lds);
   ProfScope prof(PROF_SELF_ATTN, 4.0 * (double)b * heads * (double)n * (double)n * D, s);
   const unsigned qkv_bytes = (unsigned)((int64_t)3 * b * n * heads * D * 2);
   const int grid = n_items < n_cu ? n_items / 8 * 8 : n_cu / 8 * 8;
@@ -1509,59 +1149,25 @@ static int device_cu_count() {
   return n_cu[dev];
 }
 
-// what self_attn40q_kernel asks of a launch: whole items, a tile count the four-buffer ring divides, a tensor one buffer descriptor spans, two items per CU
-static bool persistent_self_ok(int b, int n, int heads, int d, int item_queries) {
-  return n % item_queries == 0 && n % 256 == 0 && n >= 1024 && (int64_t)3 * b * n * heads * d * 2 < ((int64_t)1 << 32) && (int64_t)(n / item_queries) * heads * b >= 2 * device_cu_count();
-}
-
-bool self_attn_head_major_ok(int d, int dtype) {   // which launches read the head-major QKV planes (the 32x32x16 kernel of head_dim 40 / 80)
-  static const bool v2_80 = !env_on("ETAINV_ATT80_OLD");
-  return dtype != ETAINV_F32 && self_attn40_v2_enabled() && (d == 40 || (d == 80 && v2_80));
-}
-
 int launch_self_attention_mode(const void* qkv, void* out, int b, int n, int heads, int d, int mode, int n_img, int dtype,
                                hipStream_t s, int q_prescaled, int first_row, int head_major) {
-  ETAINV_CHECK(!head_major || self_attn_head_major_ok(d, dtype), "head-major QKV planes: head_dim 40 / 80 on the 16-bit kernel only");
+  ETAINV_CHECK((!head_major && !q_prescaled) || self_attn_prescaled_hm_ok(d, dtype), "head-major QKV planes / pre-scaled queries: head_dim 40 / 80 on the 16-bit kernels only");
   ETAINV_CHECK(qkv && out && b > 0 && n > 0, "bad arguments");
   ETAINV_CHECK(mode == 0 || (n_img > 0 && ((first_row >= 0 && b + first_row == 4 * n_img && (first_row == 0 || (first_row == n_img && mode == 1))) ||
                                            (first_row < 0 && b == 3 * n_img && mode == 1))),
                "ptp / masactrl modes need the 4*n_img backward layout (ptp: optionally without its first n_img rows, or rows [u_t, c_t, c_s] with first_row < 0)");
-  if (dtype == ETAINV_F32) {
-    ETAINV_CHECK(!q_prescaled, "fp32 path: the softmax scale is applied in the kernel");
-    return launch_self_attention_f32(qkv, out, b, n, heads, d, mode, n_img, s, first_row);
-  }
-  ETAINV_CHECK(!q_prescaled || d == 40 || d == 80, "pre-scaled queries: head_dim 40 / 80 only");
-  ETAINV_CHECK(!q_prescaled || self_attn40_v2_enabled(), "pre-scaled queries need the d = 40 kernel");
-  if (d == 40 && self_attn40_v2_enabled() && (int64_t)cdiv(n, 256) * heads * b <= 256 && n > 128) {
-    // few blocks (single-image calls: N = 4096, 8 heads, 1 row = 128 blocks of 256 queries on 256 CUs): one 32-query block per wave, twice the blocks
-    ETAINV_DISPATCH_HALF(dtype, T, return (launch_self40<T, 40, 1, 2>(qkv, out, b, n, heads, mode, n_img, q_prescaled, s, first_row, head_major)));
-  }
-  // enough (row, head, query block) items for two per CU: the persistent one-wave-per-SIMD kernel (items of 512 queries at head_dim 40, 256 at head_dim 80)
-  if (d == 40 && self_attn40_v2_enabled() && persistent_self_ok(b, n, heads, d, 512) && env_flag("ETAINV_A40_PERSIST", true)) {
-    ETAINV_DISPATCH_HALF(dtype, T, return (launch_self40q<T, 40, 4, 4>(qkv, out, b, n, heads, mode, n_img, q_prescaled, s, first_row, head_major, device_cu_count())));
-  }
-  if (d == 40 && self_attn40_v2_enabled()) {
-    // two 32-query blocks per wave, 2 waves per SIMD (one block per wave with 3 / 4 waves per SIMD: +10 % / +52 % time, re-measured in round 6 on the lean staging:
-    // profiles/r06_attention_experiments.log)
-    ETAINV_DISPATCH_HALF(dtype, T, return (launch_self40<T, 40, 2, 2>(qkv, out, b, n, heads, mode, n_img, q_prescaled, s, first_row, head_major)));
-  }
-  if (d == 80 && self_attn40_v2_enabled() && persistent_self_ok(b, n, heads, d, 256) && env_flag("ETAINV_A80_PERSIST", true)) {
-    ETAINV_DISPATCH_HALF(dtype, T, return (launch_self40q<T, 80, 2, 4>(qkv, out, b, n, heads, mode, n_img, q_prescaled, s, first_row, head_major, device_cu_count())));
-  }
-  static const bool v2_80 = !env_on("ETAINV_ATT80_OLD");   // A/B: head_dim 80 on the 32x32x16 kernel (one 32-query block per wave)
-  if (d == 80 && self_attn40_v2_enabled() && v2_80) {
-    ETAINV_DISPATCH_HALF(dtype, T, return (launch_self40<T, 80, 1, 2>(qkv, out, b, n, heads, mode, n_img, q_prescaled, s, first_row, head_major)));
-  }
-  static const bool v2_160 = env_flag("ETAINV_ATT160_V2", true);   // A/B: head_dim 160 (the (L/4)^2 level) on the 32x32x16 kernel too: one 32-query block per wave,
-  if (d == 160 && self_attn40_v2_enabled() && v2_160 && !head_major) {   // one block per CU (104 KB of K / V tiles, ~300 registers)
-    ETAINV_DISPATCH_HALF(dtype, T, return (launch_self40<T, 160, 1, 1>(qkv, out, b, n, heads, mode, n_img, q_prescaled, s, first_row, head_major)));
-  }
-  // (the generic kernel takes pre-scaled queries with scale 1: ETAINV_ATT80_OLD sends head_dim 80 here while the engine still folds the scale into to_q)
-  ETAINV_DISPATCH_HALF(dtype, T, switch (d) {
-    case 40: return launch_self_t<T, 40>(qkv, out, b, n, heads, mode, n_img, s, q_prescaled, first_row);
-    case 80: return launch_self_t<T, 80>(qkv, out, b, n, heads, mode, n_img, s, q_prescaled, first_row);
-    case 160: return launch_self_t<T, 160>(qkv, out, b, n, heads, mode, n_img, s, q_prescaled, first_row);
-    default: ETAINV_FAIL("head_dim must be 40, 80 or 160");
+  if (dtype == ETAINV_F32) return launch_self_attention_f32(qkv, out, b, n, heads, d, mode, n_img, s, first_row);
+  ETAINV_CHECK(d == 40 || d == 80 || d == 160, "head_dim must be 40, 80 or 160");
+  const int n_cu = device_cu_count();
+  // (the persist switches are read per launch: tests/test_kernels_gpu.py compares the persistent kernels with the ones they replace in one process)
+  const SelfAttnRoute route = self_attn_route(b, n, heads, d, n_cu, env_flag("ETAINV_A40_PERSIST", true), env_flag("ETAINV_A80_PERSIST", true));
+  ETAINV_DISPATCH_HALF(dtype, T, switch (route) {
+    case SELF_D40_ONE_BLOCK_PER_WAVE: return launch_self40<T, 40, 1, 2>(qkv, out, b, n, heads, mode, n_img, q_prescaled, s, first_row, head_major);
+    case SELF_D40_PERSISTENT: return launch_self40q<T, 40, 4, 4>(qkv, out, b, n, heads, mode, n_img, q_prescaled, s, first_row, head_major, n_cu);
+    case SELF_D40_TWO_BLOCK: return launch_self40<T, 40, 2, 2>(qkv, out, b, n, heads, mode, n_img, q_prescaled, s, first_row, head_major);
+    case SELF_D80_PERSISTENT: return launch_self40q<T, 80, 2, 4>(qkv, out, b, n, heads, mode, n_img, q_prescaled, s, first_row, head_major, n_cu);
+    case SELF_D80: return launch_self40<T, 80, 1, 2>(qkv, out, b, n, heads, mode, n_img, q_prescaled, s, first_row, head_major);
+    case SELF_D160: return launch_self40<T, 160, 1, 1>(qkv, out, b, n, heads, mode, n_img, q_prescaled, s, first_row, head_major);
   });
   return 0;
 }
@@ -1572,13 +1178,8 @@ static int launch_cross_t(const void* q, const void* kv, void* out, int b, const
   constexpr int DP = (D + 31) / 32 * 32, DT = (D + 15) / 16;
   const size_t lds_edit = (size_t)(2 * 96 * (DP + 8) + DT * 16 * (96 + 8)) * sizeof(T) + (size_t)(4 * QT * 16 * 81 + 4 * 80) * sizeof(float);
   const size_t lds_plain = (size_t)(96 * (DP + 8) + DT * 16 * (96 + 8)) * sizeof(T);
-  static bool attr[kMaxDevices] = {};   // per device
-  const int dev = current_device();
-  if (!attr[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cross_attn_kernel<T, D, QT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_edit);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cross_attn_kernel<T, D, QT, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_plain);
-    attr[dev] = true;
-  }
+  allow_dynamic_lds<&cross_attn_kernel<T, D, QT, true>>(lds_edit);
+  allow_dynamic_lds<&cross_attn_kernel<T, D, QT, false>>(lds_plain);
   ProfScope prof(PROF_CROSS_ATTN, 4.0 * (double)b * p.heads * (double)p.N * (double)p.n_ctx * D, s);
   const int nqb = cdiv(p.N, 64 * QT);
   auto launch = [&](bool edit, int row0, int rows) {

@@ -11,7 +11,7 @@ if [ "${EXPERIMENTS:-0}" = "1" ]; then OBJ="$HERE/obj_exp"; LIBNAME=libetainv_hi
 mkdir -p "$OUT" "$OBJ"
 pids=()
 for f in $SRCS; do
-  if [ ! -f "$OBJ/$f.o" ] || [ "$HERE/$f.hip" -nt "$OBJ/$f.o" ] || [ "$HERE/common.h" -nt "$OBJ/$f.o" ] || [ "$HERE/kernels.h" -nt "$OBJ/$f.o" ] || [ "$HERE/../../include/etainv.h" -nt "$OBJ/$f.o" ]; then
+  if [ ! -f "$OBJ/$f.o" ] || [ "$HERE/$f.hip" -nt "$OBJ/$f.o" ] || [ "$HERE/common.h" -nt "$OBJ/$f.o" ] || [ "$HERE/kernels.h" -nt "$OBJ/$f.o" ] || [ "$HERE/self_attn_route.h" -nt "$OBJ/$f.o" ] || [ "$HERE/../../include/etainv.h" -nt "$OBJ/$f.o" ]; then
     EXTRA=""
     # attention: keep MFMA results in VGPRs (the softmax consumes them on the VALU: no v_accvgpr moves) and drop the
     # NaN-canonicalising v_max the compiler inserts in front of every fmaxf on MFMA outputs
@@ -34,7 +34,7 @@ if [ "${STAMPS:-0}" = "1" ]; then
   echo "built $OUT/libetainv_hip_stamps.so"
 fi
 # A/B variant of one kernel file (same-box comparisons; boxes of the pool differ by several percent):
-#   VARIANT=name VARIANT_FILE=igemm VARIANT_FLAGS="-DETAINV_RES_PREFETCH=0" bash build.sh   ->  lib/libetainv_hip_name.so  (load with ETAINV_LIB)
+#   VARIANT=name VARIANT_FILE=igemm VARIANT_FLAGS="-DETAINV_IGEMM_STAMPS" bash build.sh   ->  lib/libetainv_hip_name.so  (load with ETAINV_LIB)
 if [ -n "${VARIANT:-}" ]; then
   vf="${VARIANT_FILE:-igemm}"
   EXTRA=""

@@ -112,6 +112,11 @@ static inline bool env_on(const char* name) {
   return v && v[0] && !(v[0] == '0' && !v[1]);
 }
 static inline bool env_flag(const char* name, bool dflt) { return getenv(name) ? env_on(name) : dflt; }
+// an integer knob: atoi of the value when the variable is set, else `dflt` (clamps stay with the caller)
+static inline int env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
 
 // one-time per-device state of the launchers (function attributes, zero pages, workspaces) is indexed by the current device
 constexpr int kMaxDevices = 16;
@@ -119,6 +124,17 @@ static inline int current_device() {
   int d = 0;
   (void)hipGetDevice(&d);
   return (d >= 0 && d < kMaxDevices) ? d : 0;
+}
+// raise a kernel's dynamic-LDS limit (launches above 64 KB need it) once per device; the state belongs to the kernel instantiation:
+//   allow_dynamic_lds<&kernel<T, ...>>(bytes);
+template <auto Kernel>
+static inline void allow_dynamic_lds(size_t bytes) {
+  static bool done[kMaxDevices] = {};
+  const int dev = current_device();
+  if (!done[dev]) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    done[dev] = true;
+  }
 }
 
 // ---- opt-in per-kernel-class timing with HIP events on the launch stream (bench.py roofline numbers).

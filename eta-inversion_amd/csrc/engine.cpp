@@ -294,7 +294,7 @@ struct Builder {
     // head_dim 40 / 80 (the L^2- and (L/2)^2-token levels): softmax scale * log2(e) folded into to_q, so that the self-attention kernel's
     // score accumulator is directly the exponent argument of exp2 (attention.hip, self_attn40_kernel) -- one rounding of W_q * c instead of
     // W_q, none added
-    if (c / etainv_engine::kHeads <= 80 && self_attn40_v2_enabled() && e->dt != ETAINV_F32)
+    if (self_attn_prescaled_hm_ok(c / etainv_engine::kHeads, e->dt))
       e->slots.back().scale = (1.0f / std::sqrt((float)(c / etainv_engine::kHeads))) * 1.4426950408889634f;
     t.q_scale = e->slots.back().scale;
     add_slot(tp + ".attn1.to_k.weight", {c, c}, &t.qkv.w, (size_t)c * c * e->esz, PK_PLAIN, 1, e->dt);
@@ -655,7 +655,7 @@ struct Fwd {
     int head_major = 0;   // the fused QKV projection writes head-major planes when both sides can (section 4.2: a 64-key tile becomes one contiguous block)
     if (fold) {
       const LnIn ln1{t.s_qkv, t.c_qkv};
-      if (e->qkv_hm && self_attn_head_major_ok(d, e->dt)) {
+      if (e->qkv_hm && self_attn_prescaled_hm_ok(d, e->dt)) {
         IGemmParams q = gemm_params(e->hsA, t.qkv, e->qkvbuf, M, &ln1);
         q.hm_heads = etainv_engine::kHeads;
         q.hm_dim = d;
@@ -671,7 +671,7 @@ struct Fwd {
       if (launch_layernorm(e->hsA, t.ln1.g, t.ln1.b, e->lnbuf, M, c, 1e-5f, e->dt, s)) return 1;
       if (gemm(e->lnbuf, t.qkv, e->qkvbuf, M)) return 1;
     }
-    if (launch_self_attention_mode(e->qkvbuf, e->attnbuf, rows, hw, etainv_engine::kHeads, d, mode, n_img, e->dt, s, /*q_prescaled=*/d <= 80 && self_attn40_v2_enabled() && e->dt != ETAINV_F32,
+    if (launch_self_attention_mode(e->qkvbuf, e->attnbuf, rows, hw, etainv_engine::kHeads, d, mode, n_img, e->dt, s, /*q_prescaled=*/self_attn_prescaled_hm_ok(d, e->dt),
                                    ctrl ? (ctrl->src_exit_block ? -1 : ctrl->first_row) : 0, head_major)) return 1;
     if (gemm(e->attnbuf, t.out1, e->hsB, M, e->hsA, 0, nullptr, 0, 0, fold)) return 1;
     if (self_rows != all_rows) {   // the other half of the batch enters the cross-attention with the same residual stream (and LayerNorm statistics)
@@ -768,7 +768,7 @@ extern "C" int etainv_engine_create(const etainv_engine_config* cfg, etainv_engi
   e->gn_fused = !env_on("ETAINV_GN_UNFUSED") && e->dt != ETAINV_F32;
   e->gn_fold = e->gn_fused && env_on("ETAINV_GN_FOLD");
   // hipGraph replay of small calls: opt-in, ETAINV_GRAPH_MAX_ROWS=<rows> (calls of at most that many UNet rows are captured and replayed)
-  if (const char* gm = getenv("ETAINV_GRAPH_MAX_ROWS")) e->graph_max_rows = atoi(gm);
+  e->graph_max_rows = env_int("ETAINV_GRAPH_MAX_ROWS", e->graph_max_rows);
   e->qkv_hm = env_flag("ETAINV_QKV_HM", true);   // (default on: +0.8 % on the benchmark step, +1 % on config 5; "0" = row-major)
   if (build_model(e) || build_workspace(e)) {
     etainv_engine_destroy(e);
@@ -1335,7 +1335,7 @@ extern "C" int etainv_op_gemm_ln_hm(const void* a, const void* w_folded, const f
   p.ln_stat = stat;
   p.ln_s = s_vec;
   *wrote_head_major = 0;
-  if (self_attn_head_major_ok(head_dim, dtype)) {
+  if (self_attn_prescaled_hm_ok(head_dim, dtype)) {
     IGemmParams q = p;
     q.hm_heads = heads;
     q.hm_dim = head_dim;

@@ -537,12 +537,7 @@ template <int D>
 static int launch_self_f32_t(const void* qkv, void* out, int b, int n, int heads, int mode, int n_img, hipStream_t s, int first_row) {
   constexpr int NT = (D + 31) / 32;
   const size_t lds = (size_t)64 * ((D + 4) + (NT * 32 + 8)) * sizeof(float);
-  static bool attr[kMaxDevices] = {};
-  const int dev = current_device();
-  if (!attr[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&self_attn_f32_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr[dev] = true;
-  }
+  allow_dynamic_lds<&self_attn_f32_kernel<D>>(lds);
   ProfScope prof(PROF_SELF_ATTN, 4.0 * (double)b * heads * (double)n * (double)n * D, s);
   hipLaunchKernelGGL(self_attn_f32_kernel<D>, dim3(cdiv(n, 128), heads, b), dim3(256), lds, s, (const float*)qkv, (float*)out, n, heads,
                      (1.0f / sqrtf((float)D)) * 1.4426950408889634f, mode, n_img, first_row);
@@ -562,12 +557,7 @@ int launch_self_attention_f32(const void* qkv, void* out, int b, int n, int head
 int launch_cross_attention_f32(const void* q, const void* kv, void* out, int b, int d, const CrossParams& p, hipStream_t s) {
   ETAINV_CHECK(p.n_ctx >= 1 && p.n_ctx <= 77 && d >= 8 && d <= 160, "fp32 cross-attention: up to 77 keys, head_dim <= 160");
   const size_t lds = (size_t)(80 * (d + 1) * 2 + 80 * d + 4 * 2 * d + 4 * 2 * 80) * sizeof(float);
-  static bool attr[kMaxDevices] = {};
-  const int dev = current_device();
-  if (!attr[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cross_attn_f32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr[dev] = true;
-  }
+  allow_dynamic_lds<&cross_attn_f32_kernel>(160 * 1024);
   ProfScope prof(PROF_CROSS_ATTN, 4.0 * (double)b * p.heads * (double)p.N * (double)p.n_ctx * d, s);
   const int gx = std::max(1, std::min(cdiv(p.N, 4), cdiv(4096, b * p.heads)));
   hipLaunchKernelGGL(cross_attn_f32_kernel, dim3(gx, p.heads, b), dim3(256), lds, s, (const float*)q, (const float*)kv, (float*)out, p, d);

@@ -467,9 +467,6 @@ __global__ void __launch_bounds__(WAVES_M * 128, 2) igemm_kernel(IGemmParams p) 
           if (p.rowvec && n < p.N) bv[j] += *reinterpret_cast<const f32x4*>(p.rowvec + (int64_t)batch * p.rowvec_stride + n);
         }
         if (ln) ln_rows(mw, ln_mean, ln_rstd);
-#ifndef ETAINV_RES_PREFETCH
-#define ETAINV_RES_PREFETCH 1
-#endif
         if (ln) {
           // LayerNorm consumer (never has a residual): its own block, so that the s vector and the row statistics do not extend the register
           // live ranges of the residual path below (256 VGPRs, no spill)
@@ -507,7 +504,6 @@ __global__ void __launch_bounds__(WAVES_M * 128, 2) igemm_kernel(IGemmParams p) 
             }
           }
         } else {
-#if ETAINV_RES_PREFETCH
         // residual: ALL of the tile's residual loads go out before the first store (MT * NT 8-byte loads per lane; the fragment registers
         // of the finished K step are dead here).  Issued per 16-row group right before that group's stores, every group exposed a full
         // memory latency with nothing else in flight: in-kernel stamps put the epilogue of a 320 -> 320 + residual GEMM at 22.6k cycles
@@ -525,35 +521,19 @@ __global__ void __launch_bounds__(WAVES_M * 128, 2) igemm_kernel(IGemmParams p) 
             }
           }
         }
-#endif
         // (a LayerNorm producer keeps the packed rows until every store is out: they take over the residual's registers row by row, and the
         // statistics run when the bias registers are dead)
         u32x2 po[MT][NT];
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
           const int m = row_m(i);
-#if !ETAINV_RES_PREFETCH
-          u32x2 rvi[NT];
-          if (res) {
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-              const int n = n0 + wn * WN + j * 16 + fq * 4;
-              rvi[j] = (u32x2){0u, 0u};
-              if (m < p.M && n < p.N) rvi[j] = *reinterpret_cast<const u32x2*>(res + (int64_t)m * p.N + n);
-            }
-          }
-#endif
 #pragma unroll
           for (int j = 0; j < NT; ++j) {
             f32x4 v = acc[i][j] + bv[j];
             acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
             if (res) {
               T r[4];
-#if ETAINV_RES_PREFETCH
               *reinterpret_cast<u32x2*>(r) = rv[i][j];
-#else
-              *reinterpret_cast<u32x2*>(r) = rvi[j];
-#endif
               v[0] += to_f32(r[0]); v[1] += to_f32(r[1]); v[2] += to_f32(r[2]); v[3] += to_f32(r[3]);
             }
             T o[4] = {from_f32<T>(v[0]), from_f32<T>(v[1]), from_f32<T>(v[2]), from_f32<T>(v[3])};
@@ -975,10 +955,6 @@ __global__ void __launch_bounds__(WAVES_M * 128, 2) igemm_kernel(IGemmParams p) 
       // (wave-uniform, masked like the source: a select would become a scalar branch in the middle of the window)
       const int dummy_el = (int)(dummy - sA), real_el = ps * (PROWS * BK) + id * 8 * BK;
       T* dst = sA + __builtin_amdgcn_readfirstlane(dummy_el + ((real_el - dummy_el) & -(int)real));
-#ifdef ETAINV_ABL_PATCH_ZERO   // timing experiment only (wrong results): every piece reads the zero page
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)zero_page, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-      return;
-#endif
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
     };
     const int kcq = cin / BK;                // channel chunks per tile (PATCH: K tile kt = q * 9 + tap)
@@ -1135,18 +1111,10 @@ __global__ void __launch_bounds__(WAVES_M * 128, 2) igemm_kernel(IGemmParams p) 
       // neither depends on the MFMAs -- so the remaining MFMAs on F0 run after the barrier, fused with window 2 into one
       // straight-line block, and a wave waiting at the barrier leaves the matrix pipe to its SIMD partner instead of both draining it
       // (stamps: counted waits + barrier were ~540 of ~2200 cycles per K step with the rendezvous between the clusters).
-#ifndef ETAINV_RING_EARLY_SYNC
-#define ETAINV_RING_EARLY_SYNC 1
-#endif
-#ifndef ETAINV_RING_NA_BASE
-#define ETAINV_RING_NA_BASE (MT + NT)
-#endif
-      constexpr int NA = (!HAS_NEXT || !ETAINV_RING_EARLY_SYNC) ? MT * NT
-                         : (ETAINV_RING_NA_BASE + (HAS_PB ? B_PASSES : 0) + 2 < MT * NT ? ETAINV_RING_NA_BASE + (HAS_PB ? B_PASSES : 0) + 2 : MT * NT);
+      constexpr int NA = !HAS_NEXT ? MT * NT : (MT + NT + (HAS_PB ? B_PASSES : 0) + 2 < MT * NT ? MT + NT + (HAS_PB ? B_PASSES : 0) + 2 : MT * NT);
       read_frags(slot, 1, fa1, fb1, ct_gq, ct_tap);
       if constexpr (HAS_PB) issue_b(pslot);
       mfma_range(fa0, fb0, std::integral_constant<int, 0>{}, std::integral_constant<int, NA>{});
-#ifndef ETAINV_W1_READS1
       // the F1 reads go two per MFMA at the head of the window: the LDS latency of the last one then lies under the rest of the cluster instead of
       // in front of the rendezvous (one per MFMA over the first nine: convs -3.0 ... -3.8 %, short-K GEMMs 0 ... -4 %)
 #pragma unroll
@@ -1155,14 +1123,6 @@ __global__ void __launch_bounds__(WAVES_M * 128, 2) igemm_kernel(IGemmParams p) 
         __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
       }
       constexpr int RSLOTS = (MT + NT + 1) / 2;   // MFMAs that carry the reads
-#else
-      constexpr int RSLOTS = MT + NT;
-#pragma unroll
-      for (int q = 0; q < MT + NT; ++q) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // 1 MFMA
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // 1 ds_read
-      }
-#endif
       if constexpr (HAS_PB) {
 #pragma unroll
         for (int q = 0; q < B_PASSES; ++q) {
@@ -1353,12 +1313,7 @@ static int launch_igemm_t(const IGemmParams& p_in, hipStream_t s, int* stat_P = 
   const int tiles = cdiv(p.M, BM) * cdiv(p.N, BN) * (STAGES != 3 && p.ksplit > 1 ? p.ksplit : 1);   // virtual tiles with split-K
   const size_t lds = (PATCH ? (size_t)(2 * 328 * 64 + STAGES * BN * BK) : (size_t)STAGES * (BM + BN) * BK) * sizeof(T) + 4 * BN * sizeof(float) + (STAGES == 3 ? 1024 : 0) +
                      (LN == 2 && STAGES == 3 && BN == 128 ? (size_t)4 * (BN + 2 * BM) * sizeof(float) : 0);   // staged s vectors and (mean, rstd) rows
-  static bool attr_set[kMaxDevices] = {};   // per device: function attributes and the allocations below belong to the current device
-  const int dev = current_device();
-  if (!attr_set[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_kernel<T, BM, BN, WAVES_M, STAGES, UPS, LN, PATCH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set[dev] = true;
-  }
+  allow_dynamic_lds<&igemm_kernel<T, BM, BN, WAVES_M, STAGES, UPS, LN, PATCH>>(lds);
   // persistent grid: as many blocks as are resident at once (LDS-limited: 160 KiB / lds per CU, 256 CUs), a multiple of 8
   const int per_cu = std::max(1, std::min(8, (int)(160 * 1024 / lds)));
   const int grid = std::min(tiles, 256 * per_cu);
@@ -1429,7 +1384,7 @@ int launch_xs_gemm(const IGemmParams&, int, hipStream_t) { ETAINV_FAIL("xsgemm.h
 #endif
 
 static int ring_min_tiles() {
-  static const int v = getenv("ETAINV_RING_MIN_TILES") ? atoi(getenv("ETAINV_RING_MIN_TILES")) : 144;
+  static const int v = env_int("ETAINV_RING_MIN_TILES", 144);
   return v;
 }
 
@@ -1465,8 +1420,8 @@ int launch_igemm(const IGemmParams& p_in, int dtype, hipStream_t s, int* stat_P)
   }
   IGemmParams p = p_in;
   p.zeros = zero_pages[dev];
-  if (const char* dbg = getenv("ETAINV_IGEMM_DEBUG")) p.debug = atoi(dbg);
-  if (const char* sg = getenv("ETAINV_STAGGER")) p.stagger = atoi(sg);
+  p.debug = env_int("ETAINV_IGEMM_DEBUG", p.debug);
+  p.stagger = env_int("ETAINV_STAGGER", p.stagger);
   ETAINV_CHECK(p.a1 && p.w && p.out, "null pointer");
   ETAINV_CHECK(p.M > 0 && p.N > 0 && (p.N % 4) == 0, "N must be a positive multiple of 4");
   ETAINV_CHECK(p.c1 % BK == 0 && p.c2 % BK == 0 && (p.c1 + p.c2) > 0, "channel counts must be multiples of 64");
@@ -1511,8 +1466,8 @@ int launch_igemm(const IGemmParams& p_in, int dtype, hipStream_t s, int* stat_P)
   // ... and for a deep K (3x3 convs of the 8x8 / 16x16 levels at a few dozen rows: 180-360 K tiles) big tiles with split-K even when they
   // alone would leave most CUs empty: 640 resident 64 x 64 blocks each walked all K tiles at one memory latency per tile (182 us per launch,
   // 1.8 % of the benchmark step)
-  static const int deepk_min_tiles = getenv("ETAINV_DEEPK_MIN_TILES") ? atoi(getenv("ETAINV_DEEPK_MIN_TILES")) : 64;
-  static const int deepk_min_nk = getenv("ETAINV_DEEPK_MIN_NK") ? atoi(getenv("ETAINV_DEEPK_MIN_NK")) : 64;
+  static const int deepk_min_tiles = env_int("ETAINV_DEEPK_MIN_TILES", 64);
+  static const int deepk_min_nk = env_int("ETAINV_DEEPK_MIN_NK", 64);
   const bool deep_k = !p.geglu && p.N % 160 == 0 && p.taps * (p.c1 + p.c2) / BK >= deepk_min_nk && !p.out_nchw && !p.out_f32 &&
                       (int64_t)cdiv(p.M, 128) * cdiv(p.N, 160) >= deepk_min_tiles;
   const bool big = p.geglu || (big_tiles >= 192 && p.N > 64) || deep_k;
@@ -1543,7 +1498,7 @@ int launch_igemm(const IGemmParams& p_in, int dtype, hipStream_t s, int* stat_P)
     // experimental (opt-in): 256 x 160 x 64 tile, 8 waves, one resident block per CU (26 % fewer L2 -> LDS bytes per
     // FLOP).  Measured equal to 128 x 160 with two resident blocks (1026 vs 1033 TFLOP/s on conv 1280->1280 @16x16)
     ETAINV_DISPATCH_HALF(dtype, T, return (launch_igemm_t<T, 256, 160, 4, 3, 0, 0>(p, s, stat_P)));
-  } else if (p.geglu && ln_ring_ok && p.c1 >= (getenv("ETAINV_GEGLU_RING_MINK") ? atoi(getenv("ETAINV_GEGLU_RING_MINK")) : 320) && (int64_t)cdiv(p.M, 256) * cdiv(p.N, 128) >= 256 && !env_on("ETAINV_NO_RING")) {
+  } else if (p.geglu && ln_ring_ok && p.c1 >= env_int("ETAINV_GEGLU_RING_MINK", 320) && (int64_t)cdiv(p.M, 256) * cdiv(p.N, 128) >= 256 && !env_on("ETAINV_NO_RING")) {
     // (since the interleaved windows the ring also wins at K = 320: 1.42 vs 1.55 ms for ff1 320 -> 2560 at 64 x 64 x 128 rows)
     ETAINV_DISPATCH_HALF(dtype, T, return (launch_igemm_t<T, 256, 128, 4, 3, 0, 0>(p, s, stat_P)));
   } else {
@@ -1560,7 +1515,7 @@ int launch_igemm(const IGemmParams& p_in, int dtype, hipStream_t s, int* stat_P)
     const int nk = p.taps * (p.c1 + p.c2) / BK;
     int ks = 1;
     if (!p.geglu && !p.out_nchw && !p.out_f32 && tiles * 2 <= slots && nk >= 16 && !env_on("ETAINV_NO_SPLITK")) {
-      static const int max_split = getenv("ETAINV_SPLITK_MAX") ? atoi(getenv("ETAINV_SPLITK_MAX")) : 32;
+      static const int max_split = env_int("ETAINV_SPLITK_MAX", 32);
       for (int d = 2; d <= max_split; ++d)
         if (nk % d == 0 && nk / d >= 4 && tiles * d <= slots && (int64_t)p.M * p.N * d * 4 <= SPLITK_WS_BYTES) ks = d;
     }

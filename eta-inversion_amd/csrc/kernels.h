@@ -121,14 +121,14 @@ int launch_ln_finalize(const float* partials, int P, int cw, float eps, float* s
 // ---- attention.hip
 // self-attention modes: 0 plain; 1 ptp self-replace (cond target rows use Q,K of their source row);
 // 2 masactrl (target rows use K,V of their source row).  Modes 1/2 need the 4*n_img backward row layout.
-// A/B switch ETAINV_ATT_OLD: head_dim 40 on the generic 16x16x32 kernel (then the engine does not fold the scale into to_q)
-bool self_attn40_v2_enabled();
-// q_prescaled (d == 40 only): the queries already carry softmax scale * log2(e) (the engine folds it into the to_q weights)
+// 16-bit launches of head_dim 40 / 80: their kernels take pre-scaled queries (the engine folds softmax scale * log2(e) into the to_q weights) and head-major
+// QKV planes (IGemmParams::hm_*).  head_dim 160 and fp32 take neither.  (Rounds 1-6 kept a generic 16x16x32 kernel behind A/B switches; it lost every A/B and is gone.)
+inline bool self_attn_prescaled_hm_ok(int d, int dtype) { return dtype != ETAINV_F32 && (d == 40 || d == 80); }
+// q_prescaled: the queries already carry softmax scale * log2(e); head_major: qkv holds three head-major planes (both: self_attn_prescaled_hm_ok launches only)
 // first_row: the call carries rows [first_row, 4 n_img) of the [u_s, u_t, c_s, c_t] x n_img layout (0, or n_img when the uncond source rows are left out:
 // backward steps with eta == 0, etainv/pipeline.py)
 int launch_self_attention_mode(const void* qkv, void* out, int b, int n, int heads, int d, int mode, int n_img, int dtype,
                                hipStream_t s, int q_prescaled = 0, int first_row = 0, int head_major = 0);
-bool self_attn_head_major_ok(int d, int dtype);
 struct CrossParams {
   int N = 0, heads = 8, n_ctx = 77;
   float scale_log2 = 0.f;

@@ -435,7 +435,7 @@ __global__ void __launch_bounds__(256) gn_finalize_kernel(const float* __restric
 // blocks of the apply pass over the whole batch (each block computes its per-lane scale / shift vectors before it streams: fewer, longer
 // blocks amortise that better)
 static inline int gn_apply_blocks() {
-  static const int n = getenv("ETAINV_GN_APPLY_BLOCKS") ? atoi(getenv("ETAINV_GN_APPLY_BLOCKS")) : 2048;
+  static const int n = env_int("ETAINV_GN_APPLY_BLOCKS", 2048);
   return n;
 }
 
@@ -465,12 +465,7 @@ int launch_groupnorm(const void* x1, const void* x2, int c1, int c2, const float
   const int vpl = ((C >> 3) + 63) / 64;
 #define ETAINV_GN_LAUNCH(VPL_)                                                                                                             \
   {                                                                                                                                        \
-    static bool attr_[kMaxDevices] = {};                                                                                                   \
-    if (!attr_[current_device()]) {                                                                                                        \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_stats_kernel<T, VPL_>), hipFuncAttributeMaxDynamicSharedMemorySize,       \
-                                4 * 64 * VPL_ * 8 * 2 * 4);                                                                                 \
-      attr_[current_device()] = true;                                                                                                      \
-    }                                                                                                                                      \
+    allow_dynamic_lds<&gn_stats_kernel<T, VPL_>>(4 * 64 * VPL_ * 8 * 2 * 4);                                                               \
     hipLaunchKernelGGL((gn_stats_kernel<T, VPL_>), dim3(chunks, b), dim3(256), lds, s, (const T*)x1, (const T*)x2, c1, c2, hw, groups, partial); \
   }
 #define ETAINV_GN_APPLY(VPL_)                                                                                                              \

@@ -822,7 +822,7 @@ bool pp_conv_applicable(const IGemmParams& p, int dtype) {
   // both ping-pong convs address with 32-bit byte offsets (buffer descriptors per image, int patch bases): larger tensors go to the ring
   const int64_t cmax = std::max(p.c1, p.N);
   if ((int64_t)p.M * cmax * 2 >= (1ll << 31) || (int64_t)p.H * p.W * cmax * 2 >= (1ll << 31)) return false;
-  static const int min_tiles = getenv("ETAINV_PPCONV_MIN_TILES") ? atoi(getenv("ETAINV_PPCONV_MIN_TILES")) : 192;
+  static const int min_tiles = env_int("ETAINV_PPCONV_MIN_TILES", 192);
   return (int64_t)(p.M / 256) * (p.N / CBN) >= min_tiles;
 }
 
@@ -843,16 +843,9 @@ int launch_pp_conv(const IGemmParams& p_in, int dtype, hipStream_t s, int* stat_
   if (pp_conv2_ok(p)) {
     const int tiles2 = (p.M / 512) * (p.N / CBN);
     const int grid2 = std::min(tiles2, 256);
-    static bool attr2_set[kMaxDevices] = {};
-    const int dev2 = current_device();
     ETAINV_DISPATCH_HALF(dtype, T, {
-      if (!attr2_set[dev2]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pp_conv2_kernel<f16, false>), hipFuncAttributeMaxDynamicSharedMemorySize, DLDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pp_conv2_kernel<f16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, DLDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pp_conv2_kernel<bf16, false>), hipFuncAttributeMaxDynamicSharedMemorySize, DLDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pp_conv2_kernel<bf16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, DLDS);
-        attr2_set[dev2] = true;
-      }
+      allow_dynamic_lds<&pp_conv2_kernel<T, false>>(DLDS);
+      allow_dynamic_lds<&pp_conv2_kernel<T, true>>(DLDS);
       if (p.stat_out) hipLaunchKernelGGL((pp_conv2_kernel<T, true>), dim3(grid2), dim3(512), DLDS, s, p);
       else hipLaunchKernelGGL((pp_conv2_kernel<T, false>), dim3(grid2), dim3(512), DLDS, s, p);
     });
@@ -861,16 +854,9 @@ int launch_pp_conv(const IGemmParams& p_in, int dtype, hipStream_t s, int* stat_
   }
   const int tiles = (p.M / 256) * (p.N / CBN);
   const int grid = std::min(tiles, 256);
-  static bool attr_set[kMaxDevices] = {};
-  const int dev = current_device();
   ETAINV_DISPATCH_HALF(dtype, T, {
-    if (!attr_set[dev]) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pp_conv_kernel<f16, false>), hipFuncAttributeMaxDynamicSharedMemorySize, CLDS);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pp_conv_kernel<f16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, CLDS);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pp_conv_kernel<bf16, false>), hipFuncAttributeMaxDynamicSharedMemorySize, CLDS);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pp_conv_kernel<bf16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, CLDS);
-      attr_set[dev] = true;
-    }
+    allow_dynamic_lds<&pp_conv_kernel<T, false>>(CLDS);
+    allow_dynamic_lds<&pp_conv_kernel<T, true>>(CLDS);
     if (p.stat_out) hipLaunchKernelGGL((pp_conv_kernel<T, true>), dim3(grid), dim3(512), CLDS, s, p);
     else hipLaunchKernelGGL((pp_conv_kernel<T, false>), dim3(grid), dim3(512), CLDS, s, p);
   });

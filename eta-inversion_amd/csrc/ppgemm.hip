@@ -946,7 +946,7 @@ static int dualn_kind(const IGemmParams& p, int dtype) {
     kind = 0;
   }
   // enough tiles, and a last round of the persistent grid that is at least 80 % full (a half-empty last round gives the -31 % DMA bytes back)
-  static const int min_tiles = getenv("ETAINV_DUALN_MIN_TILES") ? atoi(getenv("ETAINV_DUALN_MIN_TILES")) : 192;
+  static const int min_tiles = env_int("ETAINV_DUALN_MIN_TILES", 192);
   const int64_t tiles = (int64_t)(p.M / PBM) * (p.N / (kind == 3 ? 256 : 320));
   const int64_t rounds = (tiles + 255) / 256;
   if (tiles < min_tiles || tiles * 5 < rounds * 256 * 4) return -1;
@@ -957,12 +957,7 @@ bool pp_dualn_hm_ok(const IGemmParams& p, int dtype) { return dualn_kind(p, dtyp
 
 template <typename T, int HN, int EPI, bool RES, int STAT, bool A2 = false>
 static void launch_dualn_t(const IGemmParams& p, int grid, hipStream_t s) {
-  static bool attr_set[kMaxDevices] = {};
-  const int dev = current_device();
-  if (!attr_set[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pp_dualn_kernel<T, HN, EPI, RES, STAT, A2>), hipFuncAttributeMaxDynamicSharedMemorySize, DualN<HN>::LDS);
-    attr_set[dev] = true;
-  }
+  allow_dynamic_lds<&pp_dualn_kernel<T, HN, EPI, RES, STAT, A2>>(DualN<HN>::LDS);
   hipLaunchKernelGGL((pp_dualn_kernel<T, HN, EPI, RES, STAT, A2>), dim3(grid), dim3(512), DualN<HN>::LDS, s, p);
 }
 
@@ -973,7 +968,7 @@ int launch_pp_dualn(const IGemmParams& p_in, int dtype, hipStream_t s, int* stat
   if (p.stat_out) p.stat_P = p.stat_kind == 1 ? 64 : p.N / 80;   // GroupNorm: rows per partial block; LayerNorm: partials per row
   if (stat_P) *stat_P = p.stat_out ? p.stat_P : 0;
   const int tiles = (p.M / PBM) * (p.N / (kind == 3 ? 256 : 320));
-  static const int grid_cap = getenv("ETAINV_DUALN_GRID") ? std::max(1, atoi(getenv("ETAINV_DUALN_GRID"))) : 256;   // (experiments: fewer persistent blocks than CUs)
+  static const int grid_cap = std::max(1, env_int("ETAINV_DUALN_GRID", 256));   // (experiments: fewer persistent blocks than CUs)
   const int grid = std::min(tiles, grid_cap);
   ETAINV_DISPATCH_HALF(dtype, T, {
     if (kind == 3) launch_dualn_t<T, 128, 3, false, 0>(p, grid, s);
@@ -1001,21 +996,12 @@ int launch_pp_gemm(const IGemmParams& p_in, int dtype, hipStream_t s, int* stat_
   if (stat_P) *stat_P = p.stat_out ? p.stat_P : 0;
   const int tiles = (p.M / PBM) * (p.N / PBN);
   const int grid = std::min(tiles, 256);
-  static bool attr_set[kMaxDevices] = {};
-  const int dev = current_device();
   auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(512), PLDS, s, p); };
   ETAINV_DISPATCH_HALF(dtype, T, {
-    if (!attr_set[dev]) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pp_gemm_kernel<f16, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, PLDS);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pp_gemm_kernel<f16, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, PLDS);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pp_gemm_kernel<f16, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, PLDS);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pp_gemm_kernel<f16, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, PLDS);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pp_gemm_kernel<bf16, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, PLDS);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pp_gemm_kernel<bf16, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, PLDS);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pp_gemm_kernel<bf16, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, PLDS);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pp_gemm_kernel<bf16, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, PLDS);
-      attr_set[dev] = true;
-    }
+    allow_dynamic_lds<&pp_gemm_kernel<T, false, false>>(PLDS);
+    allow_dynamic_lds<&pp_gemm_kernel<T, true, false>>(PLDS);
+    allow_dynamic_lds<&pp_gemm_kernel<T, false, true>>(PLDS);
+    allow_dynamic_lds<&pp_gemm_kernel<T, true, true>>(PLDS);
     if (p.residual) {
       if (p.stat_out) go(pp_gemm_kernel<T, true, true>); else go(pp_gemm_kernel<T, true, false>);
     } else {

@@ -355,12 +355,7 @@ template <typename T, int K, int GN, bool GEGLU>
 int launch_xs_t(const XsParams& p, hipStream_t s) {
   constexpr size_t lds = (size_t)(K / XS_BK) * XS_BM * XS_BK * sizeof(T) + (size_t)4 * GN * XS_BK * sizeof(T);
   static_assert(lds <= 160 * 1024, "LDS");
-  static bool attr_set[kMaxDevices] = {};
-  const int dev = current_device();
-  if (!attr_set[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&xs_gemm_kernel<T, K, GN, GEGLU>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set[dev] = true;
-  }
+  allow_dynamic_lds<&xs_gemm_kernel<T, K, GN, GEGLU>>(lds);
   const int num_mt = p.M / XS_BM;
   const int grid = num_mt < 256 ? num_mt : 256;
 #ifdef XS_STAMPS

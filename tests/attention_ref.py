@@ -141,17 +141,21 @@ def bounds(dtype, factor=1.0):
     return TOL[dtype] * factor, TOL[dtype] * factor, QUERY_FACTOR * TOL[dtype] * factor
 
 
-def self_attention_route(b, n, heads, d, n_cu):
-    """Which kernel a 16-bit launch takes (the dispatch rules of launch_self_attention_mode, default switches); the tests assert their premises with it."""
+ROUTES = ["d40-one-block-per-wave", "d40-persistent", "d40-two-block", "d80-persistent", "d80", "d160"]   # in the order of enum SelfAttnRoute
+
+
+def self_attention_route(b, n, heads, d, n_cu, persist40=True, persist80=True):
+    """Which kernel a 16-bit launch takes; the tests assert their premises with it.  A mirror of self_attn_route (csrc/self_attn_route.h), the rule the launcher
+    switches on: test_attention_ref.py compiles that header and compares the two.  persist40 / persist80: ETAINV_A40_PERSIST / ETAINV_A80_PERSIST (default on)."""
     def persistent(item_queries):
         return (n % item_queries == 0 and n % 256 == 0 and n >= 1024 and 3 * b * n * heads * d * 2 < 1 << 32
                 and (n // item_queries) * heads * b >= 2 * n_cu)
     if d == 40:
         if -(-n // 256) * heads * b <= 256 and n > 128:
             return "d40-one-block-per-wave"
-        return "d40-persistent" if persistent(512) else "d40-two-block"
+        return "d40-persistent" if persist40 and persistent(512) else "d40-two-block"
     if d == 80:
-        return "d80-persistent" if persistent(256) else "d80"
+        return "d80-persistent" if persist80 and persistent(256) else "d80"
     return "d160"
 
 

@@ -1,6 +1,9 @@
 """CPU checks of tests/attention_ref.py: the helpers the GPU attention tests rest on, and the condition that makes their per-item bounds legitimate
 (an ideal 16-bit flash kernel -- emulate_16bit -- uses at most half of every bound on every input family those tests run)."""
+import itertools
 import math
+import pathlib
+import subprocess
 
 import pytest
 import torch
@@ -204,3 +207,50 @@ def test_coded_inputs_decode_to_the_row_maps(dtype, d, n):
     x = AR.coded_qk_qkv(4 * n_img, n, heads, d, dtype)
     wrong = AR.ref_self_attention(x, heads, maps[0], torch.arange(4 * n_img), maps[2])
     assert not torch.equal(AR.decode_tokens(wrong, heads, d), AR.expected_tokens(maps[0], maps[1], n, heads))
+
+
+# every (b, n, heads, d) that tests/test_kernels_gpu.py and tests/test_attention_forms_gpu.py launch on the 16-bit self-attention kernels
+LAUNCHED = sorted({
+    # test_kernels_gpu.py: plain
+    (2, 4096, 8, 40), (2, 1024, 8, 80), (2, 256, 8, 160), (2, 64, 8, 160), (2, 144, 8, 160), (2, 576, 8, 80),
+    # ... d40 / d80 / d160
+    (2, 256, 8, 40), (1, 64, 8, 40), (1, 144, 4, 40), (3, 200, 4, 40), (1, 576, 8, 40), (2, 1024, 8, 40), (1, 2304, 8, 40), (1, 9216, 8, 40),
+    (2, 256, 8, 80), (1, 144, 4, 80), (3, 200, 4, 80), (2, 1024, 8, 80), (1, 2304, 8, 80),
+    (4, 256, 8, 160), (2, 64, 8, 160), (1, 144, 4, 160), (3, 200, 4, 160), (1, 1024, 8, 160), (8, 256, 8, 160),
+    # ... maximum_jumps_late, single_row, speculative_maximum, the persistent-kernel tests, the remap tests, the MasaCtrl golden
+    (1, 512, 8, 40), (16, 4096, 8, 40), (1, 4096, 8, 40), (4, 2048, 8, 40),
+    (16, 2048, 8, 40), (33, 1024, 8, 40), (33, 2048, 4, 40), (9, 4096, 8, 40),
+    (16, 1024, 8, 80), (8, 2304, 8, 80), (33, 1024, 4, 80),
+    (8, 320, 8, 40), (8, 256, 8, 80), (4, 64, 8, 40),
+    # test_attention_forms_gpu.py: engine form, config 5, row layouts / item decoder (32 and 24 rows), rejected forms, projection planes, largest tensor
+    (4, 4096, 8, 40), (4, 1024, 8, 80), (16, 1024, 8, 80), (8, 9216, 8, 40), (16, 9216, 8, 40), (11, 2304, 8, 80),
+    (32, 1024, 8, 80), (24, 1024, 8, 80), (32, 2048, 8, 40), (24, 2048, 8, 40),
+    (6, 256, 8, 80), (2, 256, 8, 40),
+    (546, 4096, 8, 40), (547, 4096, 8, 40),
+})
+
+ROUTE_DRIVER = """
+#include <stdio.h>
+#include "self_attn_route.h"
+int main() {
+  int b, n, heads, d, n_cu, p40, p80;
+  while (scanf("%d %d %d %d %d %d %d", &b, &n, &heads, &d, &n_cu, &p40, &p80) == 7) printf("%d\\n", (int)etainv::self_attn_route(b, n, heads, d, n_cu, p40, p80));
+}
+"""
+
+
+def test_route_mirror_equals_the_launcher_rule(tmp_path):
+    """AR.self_attention_route against self_attn_route of csrc/self_attn_route.h (the function launch_self_attention_mode switches on), compiled with the host
+    compiler: every launched shape, 8 / 256 / 304 CUs, both settings of the two persist switches."""
+    csrc = pathlib.Path(__file__).resolve().parents[1] / "eta-inversion_amd" / "csrc"
+    (tmp_path / "driver.cpp").write_text(ROUTE_DRIVER)
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I", str(csrc), "-o", str(tmp_path / "driver"), str(tmp_path / "driver.cpp")], check=True)
+    cases = [(*shape, n_cu, p40, p80) for shape in LAUNCHED for n_cu in (8, 256, 304) for p40, p80 in itertools.product((1, 0), repeat=2)]
+    out = subprocess.run([str(tmp_path / "driver")], input="".join(" ".join(map(str, c)) + "\n" for c in cases), capture_output=True, text=True, check=True).stdout.split()
+    assert len(out) == len(cases)
+    seen = set()
+    for (b, n, heads, d, n_cu, p40, p80), got in zip(cases, out):
+        want = AR.self_attention_route(b, n, heads, d, n_cu, bool(p40), bool(p80))
+        assert AR.ROUTES[int(got)] == want, (b, n, heads, d, n_cu, p40, p80)
+        seen.add(want)
+    assert seen == set(AR.ROUTES)          # the cases reach all six routes

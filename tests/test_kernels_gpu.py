@@ -855,7 +855,7 @@ def test_self_attention_d80(capi, dtype, n, b, heads, gain):
                                                  (256, 8, 8, 1.0, 1), (256, 8, 8, 1.0, 2)])
 def test_self_attention_d160(capi, dtype, n, b, heads, gain, mode):
     """head_dim 160 (the (L/4)^2 level) on the same 32x32x16 kernel: six 32-row tiles of O^T, eleven K slices per score tile, one block per CU; ragged last
-    key tiles, the remap modes (n_img = 2), large and small score scales.  ETAINV_ATT160_V2=0 is the generic 16x16x32 kernel it replaces there."""
+    key tiles, the remap modes (n_img = 2), large and small score scales.  (It replaced the round-1 generic 16x16x32 kernel there, which is gone since.)"""
     lib = capi.load()
     d, n_img = 160, 2 if mode else 1
     qkv = rnd(b, n, 3 * heads * d, seed=n + b + 2, dtype=dtype)

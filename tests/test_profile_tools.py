@@ -11,7 +11,7 @@ KERNELS = {  # mangled names as rocprofv3 prints them for this library's templat
     "_ZN6etainv12_GLOBAL__N_114pp_conv_kernelIDF16bLb0EEEvNS_11IGemmParamsE": ("pp_conv_kernel<bf16, false>", 500.0),
     "_ZN6etainv12_GLOBAL__N_115pp_dualn_kernelIDF16bLi128ELi3ELb0ELi0EEEvNS_11IGemmParamsE": ("pp_dualn_kernel<bf16, 128, 3, false, 0>", 400.0),
     "_ZN6etainv12igemm_kernelIDF16bLi256ELi160ELi4ELi3ELi0ELi3ELb0EEEvNS_11IGemmParamsE": ("igemm_kernel<bf16, 256, 160, 4, 3, 0, 3, false>", 300.0),
-    "_ZN6etainv18self_attn40_kernelIDF16bLi40ELb1ELi2ELi2EEEvPKT_PS1_iifiiiiii": ("self_attn40_kernel<bf16, 40, true, 2, 2>", 500.0),
+    "_ZN6etainv18self_attn40_kernelIDF16bLi40ELb1ELi2ELi2EEEvPKT_PS1_iifiiiii": ("self_attn40_kernel<bf16, 40, true, 2, 2>", 500.0),
 }
 
 
