@@ -3,11 +3,8 @@
 set -e
 HERE="$(cd "$(dirname "$0")" && pwd)"
 OUT="$HERE/../etainv/lib"
-# EXPERIMENTS=1: a second library, libetainv_hip_experiments.so (objects in obj_exp/), that also carries the opt-in experiments which lost -- xsgemm.hip
-# (ETAINV_XSGEMM=1) and pp_gemm_kernel of ppgemm.hip (ETAINV_PP=1).  Load it with ETAINV_LIB=<path>; their tests skip on the default library.
 OBJ="$HERE/obj"; LIBNAME=libetainv_hip.so; SRCS="step_kernels igemm norm attention misc maps aux_nets f32path ppgemm ppconv"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result"
-if [ "${EXPERIMENTS:-0}" = "1" ]; then OBJ="$HERE/obj_exp"; LIBNAME=libetainv_hip_experiments.so; SRCS="$SRCS xsgemm"; FLAGS="$FLAGS -DETAINV_EXPERIMENTS"; fi
 mkdir -p "$OUT" "$OBJ"
 pids=()
 for f in $SRCS; do

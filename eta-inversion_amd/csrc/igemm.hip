@@ -733,12 +733,6 @@ __global__ void __launch_bounds__(WAVES_M * 128, 2) igemm_kernel(IGemmParams p) 
   };
 
   if (my_tiles <= 0) return;
-  // De-phase the two blocks that share a CU (blocks b and b + 256 of a 512-block persistent grid): they run the same tile
-  // period from the same start, so both reach their epilogues (VALU + stores, matrix pipe idle) together.  Delaying the second
-  // one by about half a tile lets each block's epilogue run under the other's matrix work.
-  if (p.stagger > 0 && ((blockIdx.x >> 8) & 1)) {
-    for (int i = 0; i < p.stagger; ++i) __builtin_amdgcn_s_sleep(1);
-  }
   const int total_steps = my_tiles * nk;
   int it_tile = 0, it_kt = 0;          // (tile, k-tile) being issued, ahead of the compute
   int ct_tile = 0, ct_kt = 0;          // (tile, k-tile) being computed
@@ -1378,35 +1372,135 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(IGemmParams p) {
   }
 }
 
-#ifndef ETAINV_EXPERIMENTS   // xsgemm.hip (stationary-activation GEMM, measured 22 % slower: profiles/HISTORY.md) is built by `EXPERIMENTS=1 build.sh` only
-bool xs_gemm_applicable(const IGemmParams&, int) { return false; }
-int launch_xs_gemm(const IGemmParams&, int, hipStream_t) { ETAINV_FAIL("xsgemm.hip is an experiment: build with EXPERIMENTS=1"); }
-#endif
-
+// the ring from this many 256 x 160 tiles on.  256 = one per CU was the round-2 threshold; the 96-row backward calls of round 3 bring 192 tiles at the
+// 8 x 8 level, where the ring on 3/4 of the CUs still beats the two-slot 128 x 160 kernel: same-box bench 4.897 (256) / 4.937 (192) / 4.910 (128) images/s.
+// Round 6: 144.  Config 5's 12 x 12 level at 32 rows is 18 x 8 = 144 tiles (1280 -> 1280 convs with 180 K tiles: 599 TFLOP/s on the two-slot kernel): same-box
+// bench config 5 0.7583 (192) / 0.7697 (144) / 0.7674 (128) / 0.7677 (96) images/s, config 3 5.801 (192) / 5.797 (128): profiles/r06_ring_min_tiles_ab.log.
+// ETAINV_RING_MIN_TILES tunes it
 static int ring_min_tiles() {
   static const int v = env_int("ETAINV_RING_MIN_TILES", 144);
   return v;
 }
+// the launch fills the 256 x 160 ring, and ETAINV_NO_RING (read per launch) does not send it to the two-slot kernels
+static bool ring_fills(const IGemmParams& p) { return (int64_t)cdiv(p.M, 256) * cdiv(p.N, 160) >= ring_min_tiles() && !env_on("ETAINV_NO_RING"); }
+// a LayerNorm consumer on a ring kernel: fast epilogue only (64-row wave tiles inside one image)
+static bool ln_ring_ok(const IGemmParams& p) { return !p.ln_stat || p.rows_per_batch % 64 == 0; }
 
-// head-major QKV output: only the LayerNorm-consumer fast path of the 256 x 160 ring implements it (the dispatch below sends exactly these launches there)
 // phase form of the fused-upsample conv (IGemmParams::ups == 2, taps == 4, weights from launch_pack_ups4): the 256 x 160 ring only, whole tiles inside
-// one phase block of one image, GroupNorm-producer or plain epilogue
+// one phase block of one image, GroupNorm-producer or plain epilogue.  (igemm_route sends every ups == 2 launch to that instantiation because launch_igemm
+// asks this predicate first: it must not ask igemm_route.)
 bool igemm_ups4_ok(const IGemmParams& p, int dtype) {
   if (dtype == ETAINV_F32 || p.taps != 4 || p.stride != 1 || p.a2 || p.geglu || p.residual || p.rowvec || p.ln_stat || p.out_f32 || p.out_nchw || p.w_batch_stride || p.pad0) return false;
   if (p.N % 160 != 0 || p.Ho != 2 * p.H || p.Wo != 2 * p.W || p.M % (4 * p.H * p.W) != 0 || p.rows_per_batch != 4 * p.H * p.W) return false;
   // whole 256-row tiles per (image, phase) -- or, in phase-major row order, per phase with 64-row wave tiles inside one image (8 x 8, 24 x 24 sources)
   if ((p.H * p.W) % 256 != 0 && ((p.M >> 2) % 256 != 0 || (p.H * p.W) % 64 != 0 || !env_flag("ETAINV_UPS4_PM", true))) return false;
   if (p.stat_out && p.stat_kind != 1) return false;
-  if (env_on("ETAINV_NO_RING") || !env_flag("ETAINV_UPS4", true)) return false;
-  return (int64_t)cdiv(p.M, 256) * cdiv(p.N, 160) >= ring_min_tiles();
+  return env_flag("ETAINV_UPS4", true) && ring_fills(p);
 }
 
+// head-major QKV output: only the LayerNorm-consumer fast path of the 256 x 160 ring implements it (igemm_route sends exactly these launches there, or to the
+// dual-N kernel, which writes the planes too).  The tail is the plain ring's condition through the shared helpers, not `igemm_route(p) == ring`: a launch
+// the dual-N kernel takes must pass as well
 bool igemm_hm_ok(const IGemmParams& p, int dtype) {
   if (dtype == ETAINV_F32 || !p.hm_heads || !p.ln_stat || p.geglu || p.taps != 1 || p.a2 || p.residual || p.stat_out || p.out_f32 || p.out_nchw || p.w_batch_stride) return false;
   if ((p.hm_dim != 40 && p.hm_dim != 80) || p.hm_heads != 8 || p.hm_tokens > 16384 || p.M >= (1 << 24)) return false;
-  if (p.N != 3 * p.hm_heads * p.hm_dim || p.N % 160 != 0 || p.hm_tokens % 256 != 0 || p.M % p.hm_tokens != 0 || p.rows_per_batch % 64 != 0) return false;
-  if (env_on("ETAINV_NO_RING") || xs_gemm_applicable(p, dtype)) return false;
-  return (int64_t)cdiv(p.M, 256) * cdiv(p.N, 160) >= ring_min_tiles();
+  if (p.N != 3 * p.hm_heads * p.hm_dim || p.N % 160 != 0 || p.hm_tokens % 256 != 0 || p.M % p.hm_tokens != 0 || !ln_ring_ok(p)) return false;
+  return ring_fills(p);
+}
+
+// ---- THE dispatch rule of the 16-bit launches (fp32 operands leave launch_igemm before it): the first condition that holds names the kernel -- their order is
+// part of the rule.  Environment switches named here are read per launch
+enum IGemmRoute { ROUTE_PPCONV, ROUTE_DUALN, ROUTE_RING_UPS4, ROUTE_RING_UPS9, ROUTE_RING_PATCH, ROUTE_RING, ROUTE_RING_GEGLU, ROUTE_TWO_SLOT };
+static const char* const kIGemmRouteName[] = {"ppconv", "dualn", "ring-ups4", "ring-ups9", "ring-patch", "ring", "ring-geglu", "two-slot"};   // ETAINV_TRACE_IGEMM, tools/launch_table.py
+
+static IGemmRoute igemm_route(const IGemmParams& p, int dtype) {
+  if (pp_conv_applicable(p, dtype)) return ROUTE_PPCONV;    // ping-pong PATCH conv3x3 (ppconv.hip)
+  if (pp_dualn_applicable(p, dtype)) return ROUTE_DUALN;    // dual-N ping-pong kernel (ppgemm.hip)
+  // conv3x3 behind a nearest-2x upsample as four 2 x 2 phase convs (4 / 9 of the FLOPs): its own instantiation of the ring (row decode, output scatter);
+  // launch_igemm has asked igemm_ups4_ok
+  if (!p.geglu && p.ups == 2) return ROUTE_RING_UPS4;
+  // the nine-tap form (images that are not whole 256-row tiles per phase): the ring's issue is branch-free, so its addressing is its own instantiation
+  if (!p.geglu && p.ups == 1 && p.N % 160 == 0 && ring_fills(p)) return ROUTE_RING_UPS9;
+  // conv3x3 stride 1 on 16-pixel-aligned images: 16 x 16 pixel patches, the halo'd activation patch of a channel chunk loaded once for all nine taps
+  // (same-box A/B, 128 rows: -1 ... -5 % per launch from the 16 x 16 level up, +1 % on the benchmark step; ETAINV_PATCHCONV=0 keeps the tap-major tiles)
+  if (!p.geglu && p.taps == 9 && p.stride == 1 && !p.ups && !p.a2 && !p.pad0 && p.H % 16 == 0 && p.W % 16 == 0 && p.H == p.Ho && p.W == p.Wo &&
+      p.N % 160 == 0 && !p.ln_stat && !p.out_nchw && !p.out_f32 && !p.w_batch_stride && (!p.stat_out || p.stat_kind == 1) &&
+      env_flag("ETAINV_PATCHCONV", true) && ring_fills(p))
+    return ROUTE_RING_PATCH;
+  // the plain ring: 256 x 160 x 64 tile, 8 waves, one resident block per CU (26 % fewer L2 -> LDS bytes per FLOP).  Measured equal to 128 x 160 with two
+  // resident blocks (1026 vs 1033 TFLOP/s on conv 1280->1280 @16x16).  (A fused upsample that did not fill the ring runs on the two-slot kernels)
+  if (!p.geglu && !p.ups && p.N % 160 == 0 && ring_fills(p) && ln_ring_ok(p)) return ROUTE_RING;
+  // the 256 x 128 ring (since the interleaved windows it also wins at K = 320: 1.42 vs 1.55 ms for ff1 320 -> 2560 at 64 x 64 x 128 rows)
+  if (p.geglu && ln_ring_ok(p) && p.c1 >= env_int("ETAINV_GEGLU_RING_MINK", 320) && (int64_t)cdiv(p.M, 256) * cdiv(p.N, 128) >= 256 && !env_on("ETAINV_NO_RING"))
+    return ROUTE_RING_GEGLU;
+  return ROUTE_TWO_SLOT;
+}
+
+// two-slot kernels: 128 x 160 (every channel count of SD1.x is a multiple of 320: no padded columns, 20 MFMAs per 9 fragment
+// reads), 128 x 128 (GEGLU / other widths), 64 x 64 for small M*N.  A two-slot block is bound by one memory latency per K tile
+// (0.62 us) whatever its tile -- 80 blocks x 180 K tiles of a 1280 -> 1280 conv at 8 x 8 took 112 us for 29.5 MB of weights --
+// so a problem that leaves resident slots empty and has a deep K is SPLIT along K (9 parts: 29 us): fp32 partials, then a
+// fixed-order reduction that applies the epilogue.
+static int launch_two_slot(const IGemmParams& p, int dtype, hipStream_t s, int* stat_P) {
+  // tile choice: big tiles when they still fill the 256 CUs, else 64x64 (GEGLU pairing is per wave tile,
+  // so the packing of a GEGLU weight fixes its tile: always 128 wide)
+  const int64_t big_tiles = (int64_t)cdiv(p.M, 128) * cdiv(p.N, 128);
+  // ... and for a deep K (3x3 convs of the 8x8 / 16x16 levels at a few dozen rows: 180-360 K tiles) big tiles with split-K even when they
+  // alone would leave most CUs empty: 640 resident 64 x 64 blocks each walked all K tiles at one memory latency per tile (182 us per launch,
+  // 1.8 % of the benchmark step)
+  static const int deepk_min_tiles = env_int("ETAINV_DEEPK_MIN_TILES", 64);
+  static const int deepk_min_nk = env_int("ETAINV_DEEPK_MIN_NK", 64);
+  const bool deep_k = !p.geglu && p.N % 160 == 0 && p.taps * (p.c1 + p.c2) / BK >= deepk_min_nk && !p.out_nchw && !p.out_f32 &&
+                      (int64_t)cdiv(p.M, 128) * cdiv(p.N, 160) >= deepk_min_tiles;
+  const bool big = p.geglu || (big_tiles >= 192 && p.N > 64) || deep_k;
+  const int cfg = (big && !p.geglu && p.N % 160 == 0) ? 0 : big ? 1 : 2;
+  const int bm = cfg == 2 ? 64 : 128, bn = cfg == 0 ? 160 : cfg == 1 ? 128 : 64;
+  // resident blocks with two LDS slots: 64 x 64 tiles 4 per CU, the others 2 per CU
+  const int slots = cfg == 2 ? 1024 : 512;
+  const int64_t tiles = (int64_t)cdiv(p.M, bm) * cdiv(p.N, bn);
+  const int nk = p.taps * (p.c1 + p.c2) / BK;
+  int ks = 1;
+  if (!p.geglu && !p.out_nchw && !p.out_f32 && tiles * 2 <= slots && nk >= 16 && !env_on("ETAINV_NO_SPLITK")) {
+    static const int max_split = env_int("ETAINV_SPLITK_MAX", 32);
+    for (int d = 2; d <= max_split; ++d)
+      if (nk % d == 0 && nk / d >= 4 && tiles * d <= slots && (int64_t)p.M * p.N * d * 4 <= SPLITK_WS_BYTES) ks = d;
+  }
+  IGemmParams pk = p;
+  if (ks > 1) {
+    // one-time 64 MiB workspace per device.  Launches on one device are serialised by the caller's stream (the engine runs one stream);
+    // concurrent split-K launches on two streams of the same device would share it.
+    static float* ws[kMaxDevices] = {};
+    const int dev = current_device();
+    if (!ws[dev]) ETAINV_HIP(hipMalloc(&ws[dev], SPLITK_WS_BYTES));
+    pk.ksplit = ks;
+    pk.ws = ws[dev];
+    pk.bias = nullptr;
+    pk.rowvec = nullptr;
+    pk.residual = nullptr;
+    pk.ln_stat = nullptr;    // applied by the reduction
+    pk.stat_out = nullptr;   // (a split-K producer emits no statistics)
+  }
+  ProfScope prof(PROF_IGEMM, 2.0 * (double)p.M * (double)p.N * (double)(p.taps * (p.c1 + p.c2)), s, igemm_algo_bytes(p));
+  prof_pause(true);
+  int rc = 0;
+  // (four LDS slots with three K tiles in flight -- the S = 4 form of the simple loop -- were measured for these kernels at batch 1: -37 % with
+  // four slots everywhere (half the resident blocks), -1.5 % when only launches whose blocks are all resident anyway took it: a K step of a
+  // lone block is bound by its own LDS-read -> MFMA chain, not by the memory latency)
+  ETAINV_DISPATCH_HALF(dtype, T, rc = cfg == 0   ? launch_igemm_t<T, 128, 160, 2, 2, 0, 0>(pk, s, stat_P)
+                                      : cfg == 1 ? launch_igemm_t<T, 128, 128, 2, 2, 0, 0>(pk, s, stat_P)
+                                                 : launch_igemm_t<T, 64, 64, 2, 2, 0, 0>(pk, s, stat_P));
+  prof_pause(false);
+  if (rc) return rc;
+  if (ks > 1) {
+    IGemmParams pr = p;
+    pr.ksplit = ks;
+    pr.ws = pk.ws;
+    const int64_t total = (int64_t)p.M * (p.N >> 2);
+    ETAINV_DISPATCH_HALF(dtype, T, hipLaunchKernelGGL(splitk_reduce_kernel<T>, dim3((unsigned)std::min<int64_t>(cdiv(total, 256), 2048)),
+                                                      dim3(256), 0, s, pr));
+    ETAINV_LAUNCH_CHECK();
+  }
+  return 0;
 }
 
 int launch_igemm(const IGemmParams& p_in, int dtype, hipStream_t s, int* stat_P) {
@@ -1421,7 +1515,6 @@ int launch_igemm(const IGemmParams& p_in, int dtype, hipStream_t s, int* stat_P)
   IGemmParams p = p_in;
   p.zeros = zero_pages[dev];
   p.debug = env_int("ETAINV_IGEMM_DEBUG", p.debug);
-  p.stagger = env_int("ETAINV_STAGGER", p.stagger);
   ETAINV_CHECK(p.a1 && p.w && p.out, "null pointer");
   ETAINV_CHECK(p.M > 0 && p.N > 0 && (p.N % 4) == 0, "N must be a positive multiple of 4");
   ETAINV_CHECK(p.c1 % BK == 0 && p.c2 % BK == 0 && (p.c1 + p.c2) > 0, "channel counts must be multiples of 64");
@@ -1435,124 +1528,32 @@ int launch_igemm(const IGemmParams& p_in, int dtype, hipStream_t s, int* stat_P)
   ETAINV_CHECK(!p.ln_stat || (!p.residual && !p.rowvec && !p.stat_out), "folded LayerNorm: no residual / row vector / statistics output on the consumer");
   ETAINV_CHECK(!p.ln_stat || (!p.out_f32 && !p.out_nchw), "folded LayerNorm: the consumer stores the compute dtype, row-major (the fp32 / NCHW epilogues do not apply mean / rstd)");
   ETAINV_CHECK(!p.hm_heads || igemm_hm_ok(p, dtype), "head-major QKV output: not available for this launch (ask igemm_hm_ok first)");
+  ETAINV_CHECK(!p.out_nchw || p.N == 4, "out_nchw needs N == 4");   // (the ping-pong kernels take no out_nchw launch)
   if (p.hm_heads) p.hm_magic = (int)(((1ull << 38) + (unsigned)p.hm_tokens - 1) / (unsigned)p.hm_tokens);   // m0 / hm_tokens == (m0 * magic) >> 38 for m0 < 2^24, hm_tokens <= 2^14
+  const IGemmRoute route = igemm_route(p, dtype);
   static const bool trace = env_on("ETAINV_TRACE_IGEMM");   // one line per launch on stderr, in launch order (tools/unet_call.py --shapes joins it with the event times)
-  if (trace) {
-    const bool ring = !p.geglu && !p.ups && p.N % 160 == 0 && (int64_t)cdiv(p.M, 256) * cdiv(p.N, 160) >= ring_min_tiles();
+  if (trace)
     fprintf(stderr, "igemm M=%d N=%d c1=%d c2=%d taps=%d stride=%d ups=%d H=%d W=%d geglu=%d ln=%d stat=%d res=%d rowvec=%d hm=%d route=%s\n", p.M, p.N, p.c1, p.c2, p.taps,
             p.stride, p.ups, p.H, p.W, (int)p.geglu, p.ln_stat ? 1 : 0, p.stat_out ? p.stat_kind : 0, p.residual ? 1 : 0, p.rowvec ? 1 : 0, p.hm_heads,
-            pp_conv_applicable(p, dtype) ? "ppconv" : pp_dualn_applicable(p, dtype) ? "dualn" : pp_gemm_applicable(p, dtype) ? "ppgemm" : xs_gemm_applicable(p, dtype) ? "xs" :
-            p.ups == 2 ? "ring-ups4" : ring ? "ring" : "other");
-  }
-  if (pp_conv_applicable(p, dtype)) {    // ping-pong PATCH conv3x3 (ppconv.hip)
-    ProfScope prof(PROF_IGEMM, 2.0 * (double)p.M * (double)p.N * (double)(9 * p.c1), s, igemm_algo_bytes(p));
-    return launch_pp_conv(p, dtype, s, stat_P);
-  }
-  if (pp_dualn_applicable(p, dtype)) {   // dual-N ping-pong kernel (ppgemm.hip)
-    ProfScope prof(PROF_IGEMM, 2.0 * (double)p.M * (double)p.N * (double)(p.c1 + p.c2), s, igemm_algo_bytes(p));
-    return launch_pp_dualn(p, dtype, s, stat_P);
-  }
-  if (pp_gemm_applicable(p, dtype)) {
-    ProfScope prof(PROF_IGEMM, 2.0 * (double)p.M * (double)p.N * (double)p.c1, s, igemm_algo_bytes(p));
-    return launch_pp_gemm(p, dtype, s, stat_P);
-  }
-  if (xs_gemm_applicable(p, dtype)) {   // K = 320 LayerNorm consumers with many rows: stationary activation tile, epilogue under the other wave group's MFMAs
-    ProfScope prof(PROF_IGEMM, 2.0 * (double)p.M * (double)p.N * (double)p.c1, s, igemm_algo_bytes(p));
-    return launch_xs_gemm(p, dtype, s);
-  }
-  // tile choice: big tiles when they still fill the 256 CUs, else 64x64 (GEGLU pairing is per wave tile,
-  // so the packing of a GEGLU weight fixes its tile: always 128 wide)
-  const int64_t big_tiles = (int64_t)cdiv(p.M, 128) * cdiv(p.N, 128);
-  // ... and for a deep K (3x3 convs of the 8x8 / 16x16 levels at a few dozen rows: 180-360 K tiles) big tiles with split-K even when they
-  // alone would leave most CUs empty: 640 resident 64 x 64 blocks each walked all K tiles at one memory latency per tile (182 us per launch,
-  // 1.8 % of the benchmark step)
-  static const int deepk_min_tiles = env_int("ETAINV_DEEPK_MIN_TILES", 64);
-  static const int deepk_min_nk = env_int("ETAINV_DEEPK_MIN_NK", 64);
-  const bool deep_k = !p.geglu && p.N % 160 == 0 && p.taps * (p.c1 + p.c2) / BK >= deepk_min_nk && !p.out_nchw && !p.out_f32 &&
-                      (int64_t)cdiv(p.M, 128) * cdiv(p.N, 160) >= deepk_min_tiles;
-  const bool big = p.geglu || (big_tiles >= 192 && p.N > 64) || deep_k;
-  ETAINV_CHECK(!p.out_nchw || p.N == 4, "out_nchw needs N == 4");
-  const int64_t huge_tiles = (int64_t)cdiv(p.M, 256) * cdiv(p.N, 160);
-  // a LayerNorm consumer on a ring kernel: fast epilogue only (64-row wave tiles inside one image)
-  const bool ln_ring_ok = !p.ln_stat || p.rows_per_batch % 64 == 0;
-  // (ring from `ring_min` 256 x 160 tiles on.  256 = one per CU was the round-2 threshold; the 96-row backward calls of round 3 bring 192 tiles at the
-  // 8 x 8 level, where the ring on 3/4 of the CUs still beats the two-slot 128 x 160 kernel: same-box bench 4.897 (256) / 4.937 (192) / 4.910 (128)
-  // images/s.  ETAINV_RING_MIN_TILES tunes it)
-  // Round 6: 144.  Config 5's 12 x 12 level at 32 rows is 18 x 8 = 144 tiles (1280 -> 1280 convs with 180 K tiles: 599 TFLOP/s on the two-slot kernel): same-box
-  // bench config 5 0.7583 (192) / 0.7697 (144) / 0.7674 (128) / 0.7677 (96) images/s, config 3 5.801 (192) / 5.797 (128): profiles/r06_ring_min_tiles_ab.log)
-  static const int ring_min = ring_min_tiles();
-  if (!p.geglu && p.ups == 2) {
-    p.ups_pm = (p.H * p.W) % 256 != 0;
-    // conv3x3 behind a nearest-2x upsample as four 2 x 2 phase convs (4 / 9 of the FLOPs): its own instantiation of the ring (row decode, output scatter)
-    ETAINV_DISPATCH_HALF(dtype, T, return (launch_igemm_t<T, 256, 160, 4, 3, 2, 0>(p, s, stat_P)));
-  } else if (!p.geglu && p.ups == 1 && p.N % 160 == 0 && huge_tiles >= ring_min && !env_on("ETAINV_NO_RING")) {
-    // the nine-tap form (images that are not whole 256-row tiles per phase): the ring's issue is branch-free, so its addressing is its own instantiation
-    ETAINV_DISPATCH_HALF(dtype, T, return (launch_igemm_t<T, 256, 160, 4, 3, 1, 0>(p, s, stat_P)));
-  } else if (!p.geglu && p.taps == 9 && p.stride == 1 && !p.ups && !p.a2 && !p.pad0 && p.H % 16 == 0 && p.W % 16 == 0 && p.H == p.Ho && p.W == p.Wo &&
-             p.N % 160 == 0 && huge_tiles >= ring_min && !p.ln_stat && !p.out_nchw && !p.out_f32 && !p.w_batch_stride &&
-             (!p.stat_out || p.stat_kind == 1) && env_flag("ETAINV_PATCHCONV", true) && !env_on("ETAINV_NO_RING")) {
-    // conv3x3 stride 1 on 16-pixel-aligned images: 16 x 16 pixel patches, the halo'd activation patch of a channel chunk loaded once for all nine taps
-    // (same-box A/B, 128 rows: -1 ... -5 % per launch from the 16 x 16 level up, +1 % on the benchmark step; ETAINV_PATCHCONV=0 keeps the tap-major tiles)
-    ETAINV_DISPATCH_HALF(dtype, T, return (launch_igemm_t<T, 256, 160, 4, 3, 0, 0, true>(p, s, stat_P)));
-  } else if (!p.geglu && !p.ups && p.N % 160 == 0 && huge_tiles >= ring_min && ln_ring_ok && !env_on("ETAINV_NO_RING")) {   // (a fused upsample that did not fill the ring runs on the two-slot kernels below)
-    // experimental (opt-in): 256 x 160 x 64 tile, 8 waves, one resident block per CU (26 % fewer L2 -> LDS bytes per
-    // FLOP).  Measured equal to 128 x 160 with two resident blocks (1026 vs 1033 TFLOP/s on conv 1280->1280 @16x16)
-    ETAINV_DISPATCH_HALF(dtype, T, return (launch_igemm_t<T, 256, 160, 4, 3, 0, 0>(p, s, stat_P)));
-  } else if (p.geglu && ln_ring_ok && p.c1 >= env_int("ETAINV_GEGLU_RING_MINK", 320) && (int64_t)cdiv(p.M, 256) * cdiv(p.N, 128) >= 256 && !env_on("ETAINV_NO_RING")) {
-    // (since the interleaved windows the ring also wins at K = 320: 1.42 vs 1.55 ms for ff1 320 -> 2560 at 64 x 64 x 128 rows)
-    ETAINV_DISPATCH_HALF(dtype, T, return (launch_igemm_t<T, 256, 128, 4, 3, 0, 0>(p, s, stat_P)));
-  } else {
-    // two-slot kernels: 128 x 160 (every channel count of SD1.x is a multiple of 320: no padded columns, 20 MFMAs per 9 fragment
-    // reads), 128 x 128 (GEGLU / other widths), 64 x 64 for small M*N.  A two-slot block is bound by one memory latency per K tile
-    // (0.62 us) whatever its tile -- 80 blocks x 180 K tiles of a 1280 -> 1280 conv at 8 x 8 took 112 us for 29.5 MB of weights --
-    // so a problem that leaves resident slots empty and has a deep K is SPLIT along K (9 parts: 29 us): fp32 partials, then a
-    // fixed-order reduction that applies the epilogue.
-    const int cfg = (big && !p.geglu && p.N % 160 == 0) ? 0 : big ? 1 : 2;
-    const int bm = cfg == 2 ? 64 : 128, bn = cfg == 0 ? 160 : cfg == 1 ? 128 : 64;
-    // resident blocks with two LDS slots: 64 x 64 tiles 4 per CU, the others 2 per CU
-    const int slots = cfg == 2 ? 1024 : 512;
-    const int64_t tiles = (int64_t)cdiv(p.M, bm) * cdiv(p.N, bn);
-    const int nk = p.taps * (p.c1 + p.c2) / BK;
-    int ks = 1;
-    if (!p.geglu && !p.out_nchw && !p.out_f32 && tiles * 2 <= slots && nk >= 16 && !env_on("ETAINV_NO_SPLITK")) {
-      static const int max_split = env_int("ETAINV_SPLITK_MAX", 32);
-      for (int d = 2; d <= max_split; ++d)
-        if (nk % d == 0 && nk / d >= 4 && tiles * d <= slots && (int64_t)p.M * p.N * d * 4 <= SPLITK_WS_BYTES) ks = d;
+            kIGemmRouteName[route]);
+  switch (route) {
+    case ROUTE_PPCONV: {
+      ProfScope prof(PROF_IGEMM, 2.0 * (double)p.M * (double)p.N * (double)(9 * p.c1), s, igemm_algo_bytes(p));
+      return launch_pp_conv(p, dtype, s, stat_P);
     }
-    IGemmParams pk = p;
-    if (ks > 1) {
-      // one-time 64 MiB workspace per device.  Launches on one device are serialised by the caller's stream (the engine runs one stream);
-      // concurrent split-K launches on two streams of the same device would share it.
-      static float* ws[kMaxDevices] = {};
-      if (!ws[dev]) ETAINV_HIP(hipMalloc(&ws[dev], SPLITK_WS_BYTES));
-      pk.ksplit = ks;
-      pk.ws = ws[dev];
-      pk.bias = nullptr;
-      pk.rowvec = nullptr;
-      pk.residual = nullptr;
-      pk.ln_stat = nullptr;    // applied by the reduction
-      pk.stat_out = nullptr;   // (a split-K producer emits no statistics)
+    case ROUTE_DUALN: {
+      ProfScope prof(PROF_IGEMM, 2.0 * (double)p.M * (double)p.N * (double)(p.c1 + p.c2), s, igemm_algo_bytes(p));
+      return launch_pp_dualn(p, dtype, s, stat_P);
     }
-    ProfScope prof(PROF_IGEMM, 2.0 * (double)p.M * (double)p.N * (double)(p.taps * (p.c1 + p.c2)), s, igemm_algo_bytes(p));
-    prof_pause(true);
-    int rc = 0;
-    // (four LDS slots with three K tiles in flight -- the S = 4 form of the simple loop -- were measured for these kernels at batch 1: -37 % with
-    // four slots everywhere (half the resident blocks), -1.5 % when only launches whose blocks are all resident anyway took it: a K step of a
-    // lone block is bound by its own LDS-read -> MFMA chain, not by the memory latency)
-    ETAINV_DISPATCH_HALF(dtype, T, rc = cfg == 0   ? launch_igemm_t<T, 128, 160, 2, 2, 0, 0>(pk, s, stat_P)
-                                        : cfg == 1 ? launch_igemm_t<T, 128, 128, 2, 2, 0, 0>(pk, s, stat_P)
-                                                   : launch_igemm_t<T, 64, 64, 2, 2, 0, 0>(pk, s, stat_P));
-    prof_pause(false);
-    if (rc) return rc;
-    if (ks > 1) {
-      IGemmParams pr = p;
-      pr.ksplit = ks;
-      pr.ws = pk.ws;
-      const int64_t total = (int64_t)p.M * (p.N >> 2);
-      ETAINV_DISPATCH_HALF(dtype, T, hipLaunchKernelGGL(splitk_reduce_kernel<T>, dim3((unsigned)std::min<int64_t>(cdiv(total, 256), 2048)),
-                                                        dim3(256), 0, s, pr));
-      ETAINV_LAUNCH_CHECK();
-    }
+    case ROUTE_RING_UPS4:
+      p.ups_pm = (p.H * p.W) % 256 != 0;
+      ETAINV_DISPATCH_HALF(dtype, T, return (launch_igemm_t<T, 256, 160, 4, 3, 2, 0>(p, s, stat_P)));
+      break;
+    case ROUTE_RING_UPS9: ETAINV_DISPATCH_HALF(dtype, T, return (launch_igemm_t<T, 256, 160, 4, 3, 1, 0>(p, s, stat_P))); break;
+    case ROUTE_RING_PATCH: ETAINV_DISPATCH_HALF(dtype, T, return (launch_igemm_t<T, 256, 160, 4, 3, 0, 0, true>(p, s, stat_P))); break;
+    case ROUTE_RING: ETAINV_DISPATCH_HALF(dtype, T, return (launch_igemm_t<T, 256, 160, 4, 3, 0, 0>(p, s, stat_P))); break;
+    case ROUTE_RING_GEGLU: ETAINV_DISPATCH_HALF(dtype, T, return (launch_igemm_t<T, 256, 128, 4, 3, 0, 0>(p, s, stat_P))); break;
+    case ROUTE_TWO_SLOT: return launch_two_slot(p, dtype, s, stat_P);
   }
   return 0;
 }

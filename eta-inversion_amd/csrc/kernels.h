@@ -27,7 +27,6 @@ struct IGemmParams {
   // consumer on the 256 x 160 ring, hm_dim 40 / 80, whole tiles inside one batch row).  0 = row-major
   int hm_heads = 0, hm_dim = 0, hm_tokens = 0, hm_magic = 0;   // (hm_magic: filled in by launch_igemm)
   unsigned long* stamps = nullptr;         // diagnostic build (-DETAINV_IGEMM_STAMPS) only
-  int stagger = 0;                  // experiment (ETAINV_STAGGER): start delay of the second co-resident block, 64-cycle ticks
   int M = 0, N = 0;
   int c1 = 0, c2 = 0;
   int H = 1, W = 1;           // source spatial dims (before the fused upsample)
@@ -63,15 +62,7 @@ int launch_igemm(const IGemmParams& p, int dtype, hipStream_t s, int* stat_P = n
 bool igemm_hm_ok(const IGemmParams& p, int dtype);     // may this launch (with hm_* set) write the head-major layout?
 bool igemm_ups4_ok(const IGemmParams& p, int dtype);   // may this launch run the phase form (ups == 2, taps == 4) of a fused-upsample conv?
 
-// ---- xsgemm.hip: K = 320 LayerNorm-consumer projections (GEGLU, fused QKV) of the L^2-token blocks on a stationary activation tile with two wave
-// groups in anti-phase; launch_igemm routes to it when xs_gemm_applicable (bit-identical results)
-bool xs_gemm_applicable(const IGemmParams& p, int dtype);
-int launch_xs_gemm(const IGemmParams& p, int dtype, hipStream_t s);
-
-// ---- ppgemm.hip: the 256 x 160 tile with its two wave groups in anti-phase (ping-pong) and the epilogue of a tile under the next tile's main loop (two
-// accumulator sets): 1x1 / Linear with bias (+ residual, + LayerNorm row statistics), K >= 320; launch_igemm routes to it when pp_gemm_applicable
-bool pp_gemm_applicable(const IGemmParams& p, int dtype);
-int launch_pp_gemm(const IGemmParams& p, int dtype, hipStream_t s, int* stat_P = nullptr);
+// ---- ppgemm.hip: the dual-N ping-pong GEMM; launch_igemm routes to it when pp_dualn_applicable.
 // dual-N form: a 256 x 320 output tile as two 160-column halves sharing one staged activation K tile (-31 % LDS-DMA bytes per FLOP; the 1x1 GEMMs are bound
 // by the DMA fill rate): bias (+ residual) (+ LayerNorm row statistics), LayerNorm consumer (row-major / head-major QKV planes), and -- as a 256 x 256 tile
 // of two 128-column halves -- the LayerNorm-consumer GEGLU projection

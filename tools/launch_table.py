@@ -4,6 +4,11 @@ with the event times of the same launches (tools/unet_call.py --shapes --dump) a
 
     ETAINV_TRACE_IGEMM=1 python tools/unet_call.py --rows 128 --calls 2 --shapes --dump launches.json 2> trace.txt
     python tools/launch_table.py launches.json trace.txt
+
+route= is the name of the route launch_igemm took (igemm.hip igemm_route): ppconv, dualn, ring-ups4, ring-ups9, ring-patch, ring, ring-geglu, two-slot.
+Traces and tables made before igemm_route existed (the per-route tables of DESIGN.md among them) came from a shortened copy of the rule: their `ring`
+also covers launches that ran on the two-slot kernels (a LayerNorm consumer with rows_per_batch % 64 != 0, ETAINV_NO_RING) and the PATCH ring, and their
+`other` lumps the GEGLU ring, the nine-tap upsample ring and the two-slot kernels together.
 """
 import collections
 import json

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Ping-pong GEMM (ppgemm.hip, opt-in: ETAINV_PP=1; ETAINV_PP_FORCE_ALL=1 also takes the residual / statistics variants, which spill) against the ring kernel on the same inputs: equality and time.  GPU box only.
-    python tools/pp_check.py [dualn] [res] [stat]     # dualn: the dual-N kernel (ETAINV_DUALN) instead; which epilogue variants to include
-(round 6: pp_gemm_kernel (ETAINV_PP=1) is in the EXPERIMENTS=1 library only (ETAINV_LIB=.../libetainv_hip_experiments.so); the dual-N modes run on the default library)"""
+"""Dual-N ping-pong GEMM (ppgemm.hip; ETAINV_DUALN=0 switches it off) against the ring kernel on the same inputs: equality and time.  GPU box only.
+    python tools/pp_check.py dualn [res] [stat] [ln] [ablate] [convablate]     # which epilogue variants / further sections to include
+(`dualn` is accepted and ignored: it used to select this kernel instead of its round-5 predecessor, see tools/experiments/gemm_r05/README.md)"""
 import ctypes as C
 import os
 import sys
@@ -16,7 +16,7 @@ lib = _capi.load()
 st = _capi.stream_ptr()
 dt = torch.bfloat16
 code = _capi.dtype_code(dt)
-SWITCH = "ETAINV_DUALN" if "dualn" in sys.argv else "ETAINV_PP"
+SWITCH = "ETAINV_DUALN"
 variants = [(False, False)] + ([(True, False)] if "res" in sys.argv else []) + ([(False, True), (True, True)] if "stat" in sys.argv else [])
 
 
