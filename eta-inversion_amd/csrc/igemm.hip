@@ -1465,6 +1465,8 @@ static int launch_two_slot(const IGemmParams& p, int dtype, hipStream_t s, int* 
     for (int d = 2; d <= max_split; ++d)
       if (nk % d == 0 && nk / d >= 4 && tiles * d <= slots && (int64_t)p.M * p.N * d * 4 <= SPLITK_WS_BYTES) ks = d;
   }
+  static const bool trace = env_on("ETAINV_TRACE_IGEMM");   // behind launch_igemm's line: the tile and the K split this launch takes
+  if (trace) fprintf(stderr, "  two-slot tile=%dx%d ksplit=%d\n", bm, bn, ks);
   IGemmParams pk = p;
   if (ks > 1) {
     // one-time 64 MiB workspace per device.  Launches on one device are serialised by the caller's stream (the engine runs one stream);

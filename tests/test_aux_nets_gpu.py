@@ -1,5 +1,7 @@
 """VAE encode/decode and CLIP text encoder on the native kernels vs the CPU oracle (oracle/vae.py, oracle/clip.py), same
-seeded synthetic weights by name.  Tolerance: fp16 operands / fp32 accumulation, relative L2 <= 5e-3 (bf16: 3e-2)."""
+seeded synthetic weights by name.  Tolerance: fp16 operands / fp32 accumulation, relative L2 <= 5e-3 (bf16: 3e-2).
+These are whole-network norms; every kernel these networks launch is pinned per op (borders, planes, tiles, guards) in
+tests/test_aux_kernels_gpu.py."""
 import pytest
 import torch
 
