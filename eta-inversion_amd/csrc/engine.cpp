@@ -46,7 +46,7 @@ void prof_begin(int cls, double work, hipStream_t s, double bytes) {
 }
 void prof_end(hipStream_t s) { (void)hipEventRecord(g_prof.back().b, s); }
 
-enum PackMode { PK_PLAIN = 0, PK_CONV = 1, PK_GEGLU = 2, PK_CONV_IN = 3, PK_CONV_OUT = 4, PK_CONV_IN_GEMM = 5 };
+enum PackMode { PK_PLAIN = 0, PK_CONV = 1, PK_GEGLU = 2, PK_CONV_IN_GEMM = 5 };   // (3 and 4 were the direct conv_in / conv_out kernels' layouts: retired)
 
 struct WeightSlot {
   std::string name;
@@ -1442,31 +1442,14 @@ extern "C" int etainv_op_pack_ups4(const float* w_oc33, void* dst, int cout, int
   return launch_pack_ups4(w_oc33, dst, cout, cin, dtype, (hipStream_t)stream);
 }
 
+extern "C" int etainv_op_conv3x3_rv(const void* x_nhwc, const void* x2_nhwc, int c1, int c2, const void* w_okkc, const void* bias, const float* rowvec,
+                                    int rowvec_stride, const void* residual, void* out, int b, int h, int wd, int cout, int stride, int upsample, int taps,
+                                    int dtype, void* stream);
+// the time row as its own dense [b][cout] matrix
 extern "C" int etainv_op_conv3x3(const void* x_nhwc, const void* x2_nhwc, int c1, int c2, const void* w_okkc, const void* bias,
                                  const float* rowvec, const void* residual, void* out, int b, int h, int wd, int cout, int stride,
                                  int upsample, int taps, int dtype, void* stream) {
-  IGemmParams p;
-  p.a1 = x_nhwc;
-  p.a2 = x2_nhwc;
-  p.w = w_okkc;
-  p.bias = (const float*)bias;
-  p.rowvec = rowvec;
-  p.rowvec_stride = cout;
-  p.residual = residual;
-  p.out = out;
-  p.c1 = c1;
-  p.c2 = c2;
-  p.H = h;
-  p.W = wd;
-  p.Ho = upsample ? h * 2 : (stride == 2 ? h / 2 : h);
-  p.Wo = upsample ? wd * 2 : (stride == 2 ? wd / 2 : wd);
-  p.stride = stride;
-  p.ups = upsample;
-  p.taps = taps;
-  p.M = b * p.Ho * p.Wo;
-  p.N = cout;
-  p.rows_per_batch = p.Ho * p.Wo;
-  return launch_igemm(p, dtype, (hipStream_t)stream);
+  return etainv_op_conv3x3_rv(x_nhwc, x2_nhwc, c1, c2, w_okkc, bias, rowvec, cout, residual, out, b, h, wd, cout, stride, upsample, taps, dtype, stream);
 }
 
 extern "C" int etainv_op_groupnorm(const void* x_nhwc, const void* x2_nhwc, int c1, int c2, const float* gamma, const float* beta,
@@ -1516,6 +1499,117 @@ extern "C" int etainv_op_cross_attention(const void* q, const void* kv, void* ou
     if (ctrl->store_maps && maps_acc) cp.map_layer = map_layer;
   }
   return launch_cross_attention_p(q, kv, out, b, d, cp, dtype, (hipStream_t)stream);
+}
+
+// conv3x3 (+ second source, fused upsample, stride 2) with the time row read the way the UNet reads it: rowvec points at this layer's columns inside the
+// [b][rowvec_stride] fp32 matrix of all time projections
+extern "C" int etainv_op_conv3x3_rv(const void* x_nhwc, const void* x2_nhwc, int c1, int c2, const void* w_okkc, const void* bias,
+                                    const float* rowvec, int rowvec_stride, const void* residual, void* out, int b, int h, int wd, int cout,
+                                    int stride, int upsample, int taps, int dtype, void* stream) {
+  ETAINV_CHECK(!rowvec || rowvec_stride >= cout, "rowvec_stride must cover the cout columns of a row");
+  IGemmParams p;
+  p.a1 = x_nhwc;
+  p.a2 = x2_nhwc;
+  p.w = w_okkc;
+  p.bias = (const float*)bias;
+  p.rowvec = rowvec;
+  p.rowvec_stride = rowvec_stride;
+  p.residual = residual;
+  p.out = out;
+  p.c1 = c1;
+  p.c2 = c2;
+  p.H = h;
+  p.W = wd;
+  p.Ho = upsample ? h * 2 : (stride == 2 ? h / 2 : h);
+  p.Wo = upsample ? wd * 2 : (stride == 2 ? wd / 2 : wd);
+  p.stride = stride;
+  p.ups = upsample;
+  p.taps = taps;
+  p.M = b * p.Ho * p.Wo;
+  p.N = cout;
+  p.rows_per_batch = p.Ho * p.Wo;
+  return launch_igemm(p, dtype, (hipStream_t)stream);
+}
+
+// the GEMM of all time-embedding projections as unet_body launches it: fp32 output [m][n]
+extern "C" int etainv_op_gemm_f32out(const void* a, const void* w, const float* bias, float* out_f32, int m, int n, int k, int dtype, void* stream) {
+  IGemmParams p;
+  p.a1 = a;
+  p.w = w;
+  p.bias = bias;
+  p.out = out_f32;
+  p.out_f32 = 1;
+  p.M = m;
+  p.N = n;
+  p.c1 = k;
+  p.W = m;
+  p.Wo = m;
+  p.rows_per_batch = m;
+  return launch_igemm(p, dtype, (hipStream_t)stream);
+}
+
+extern "C" int etainv_op_gn_fold(const float* w, const float* gamma, const float* beta, const float* bias, const float* stats, int groups, int b, int n,
+                                 int k, void* wb_out, float* cb_out, int dtype, void* stream) {
+  return launch_gn_fold(w, gamma, beta, bias, stats, groups, b, n, k, wb_out, cb_out, dtype, (hipStream_t)stream);
+}
+
+// the 1x1 conv behind a folded GroupNorm as Fwd::gemm launches it: image i (hw rows) multiplies wb[i] [n][k] and adds cb[i] [n]
+extern "C" int etainv_op_gemm_per_image(const void* a, const void* wb, const float* cb, const void* residual, void* out, int b, int hw, int n, int k,
+                                        int dtype, void* stream) {
+  ETAINV_CHECK(b > 0 && hw > 0, "bad sizes");
+  IGemmParams p;
+  p.a1 = a;
+  p.w = wb;
+  p.bias = cb;
+  p.residual = residual;
+  p.out = out;
+  p.M = b * hw;
+  p.N = n;
+  p.c1 = k;
+  p.W = p.M;
+  p.Wo = p.M;
+  p.rows_per_batch = hw;
+  p.w_batch_stride = (int64_t)n * k;
+  p.bias_batch_stride = n;
+  return launch_igemm(p, dtype, (hipStream_t)stream);
+}
+
+// via_device = 0: timesteps by value in the kernel arguments; 1: through the device vector t_dev [rows] (the captured-graph route)
+extern "C" int etainv_op_time_embedding(const int64_t* t_host, int rows, int dim, void* out, int dtype, int via_device, float* t_dev, void* stream) {
+  if (!via_device) return launch_time_embedding(t_host, rows, dim, out, dtype, (hipStream_t)stream);
+  ETAINV_CHECK(t_dev, "via_device needs t_dev");
+  if (launch_set_timesteps(t_host, rows, t_dev, (hipStream_t)stream)) return 1;
+  return launch_time_embedding_dev(t_dev, rows, dim, out, dtype, (hipStream_t)stream);
+}
+
+extern "C" int etainv_op_silu(const void* x, void* out, int64_t n, int dtype, void* stream) {
+  ETAINV_CHECK(x && out && n >= 0, "null pointer or negative size");
+  if (n == 0) return 0;
+  return launch_silu(x, out, n, dtype, (hipStream_t)stream);
+}
+
+extern "C" int etainv_op_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, void* stream) {
+  ETAINV_CHECK(src && dst && n >= 0, "null pointer or negative size");
+  if (n == 0) return 0;
+  return launch_cast_f32(src, src_dtype, dst, dst_dtype, n, (hipStream_t)stream);
+}
+
+extern "C" int etainv_op_im2col_in(const void* latent, int io_dtype, int n_lat, int rows, int l, void* out, int dtype, void* stream) {
+  ETAINV_CHECK(l > 0, "bad sizes");
+  return launch_im2col_in(latent, io_dtype, n_lat, rows, l, out, dtype, (hipStream_t)stream);
+}
+
+extern "C" int etainv_op_pack_weight(const float* src, void* dst, int64_t rows, int64_t cols, int mode, int taps, float scale, const float* colscale,
+                                     int dtype, void* stream) {
+  return launch_pack_weight(src, dst, rows, cols, mode, taps, dtype, (hipStream_t)stream, scale, colscale);
+}
+
+extern "C" int etainv_op_word_maps_ex(const float* maps_acc, int n_layers, int n_img_cap, int heads, int res, int L, int n_img, const int32_t* tokens,
+                                      int n_tok, int steps_done, int row_sel, unsigned layer_mask, float* out, int accumulate, float scale, void* stream) {
+  ETAINV_CHECK(row_sel == 0 || row_sel == 1, "row_sel: 0 = source cond row, 1 = target cond row");
+  ETAINV_CHECK(n_img <= n_img_cap && heads > 0 && res > 0 && L > 0, "bad sizes");
+  return launch_word_maps(maps_acc, n_layers, n_img_cap, 2, row_sel, heads, res, L, n_img, tokens, n_tok, steps_done, out, accumulate, scale,
+                          (hipStream_t)stream, layer_mask);
 }
 
 extern "C" int etainv_op_word_maps(const float* maps_acc, int n_layers, int n_img_cap, int heads, int res, int L, int n_img,

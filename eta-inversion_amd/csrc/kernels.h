@@ -141,14 +141,8 @@ struct CrossParams {
 int launch_cross_attention_p(const void* q, const void* kv, void* out, int b, int d, const CrossParams& p, int dtype, hipStream_t s);
 
 // ---- misc.hip
-// conv_in: NCHW io-dtype latent [n_lat][4][L][L] (row r reads r % n_lat) -> NHWC T [rows][L*L][cout], 3x3 pad 1
-int launch_conv_in(const void* latent, int io_dtype, int n_lat, int rows, int L, const void* w, const float* bias, int cout,
-                   void* out, int dtype, hipStream_t s);
-// im2col of the 3x3 / 4-channel input conv: NCHW io-dtype latent [n_lat][4][L][L] -> T [rows][L*L][64] (k = tap*4 + ci, 36..63 zero)
+// im2col of the 3x3 / 4-channel input conv: NCHW io-dtype latent [n_lat][4][L][L] (row r reads r % n_lat) -> T [rows][L*L][64] (k = tap*4 + ci, 36..63 zero)
 int launch_im2col_in(const void* latent, int io_dtype, int n_lat, int rows, int L, void* out, int dtype, hipStream_t s);
-// conv_out: NHWC T [rows][L*L][cin] (already GroupNorm+SiLU'd) -> NCHW io-dtype [rows][4][L][L]
-int launch_conv_out(const void* x, int rows, int L, int cin, const void* w, const float* bias, void* out, int io_dtype, int dtype,
-                    hipStream_t s);
 // sinusoidal timestep embedding (flip_sin_to_cos, freq_shift 0): t_host [rows] (HOST array, passed by value in the kernel arguments) -> [rows][dim] T
 int launch_time_embedding(const int64_t* t_host, int rows, int dim, void* out, int dtype, hipStream_t s);
 // the same from DEVICE timesteps t_dev [rows] floats (written by launch_set_timesteps): replayable inside a captured hipGraph

@@ -88,6 +88,16 @@ SIGNATURES = {
     "etainv_op_cross_attention": [_p, _p, _p, _i, _i, _i, _i, _i, C.POINTER(AttnCtrl), _i, _i, _p, _i, _p],
     "etainv_op_word_maps": [_p, _i, _i, _i, _i, _i, _i, _p, _i, _i, _p, _i, _f, _p],
     "etainv_op_local_blend": [_p, _i, _i, _i, _i, _i, _p, _i, _p, _f, _p],
+    "etainv_op_word_maps_ex": [_p, _i, _i, _i, _i, _i, _i, _p, _i, _i, _i, C.c_uint, _p, _i, _f, _p],
+    "etainv_op_time_embedding": [C.POINTER(_i64), _i, _i, _p, _i, _i, _p, _p],
+    "etainv_op_silu": [_p, _p, _i64, _i, _p],
+    "etainv_op_cast": [_p, _i, _p, _i, _i64, _p],
+    "etainv_op_im2col_in": [_p, _i, _i, _i, _i, _p, _i, _p],
+    "etainv_op_pack_weight": [_p, _p, _i64, _i64, _i, _i, _f, _p, _i, _p],
+    "etainv_op_gemm_f32out": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "etainv_op_conv3x3_rv": [_p, _p, _i, _i, _p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "etainv_op_gn_fold": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _i, _p],
+    "etainv_op_gemm_per_image": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
 }
 _RESTYPES = {"etainv_last_error": C.c_char_p, "etainv_engine_workspace_bytes": _i64, "etainv_engine_weight_bytes": _i64}
 

@@ -318,6 +318,42 @@ int etainv_op_word_maps(const float* maps_acc, int n_layers, int n_img_cap, int 
 int etainv_op_local_blend(const float* maps_acc, int n_layers, int n_img_cap, int heads, int res, int L, float* x,
                           int n_img, const float* blend_alpha, float thres, void* stream);
 
+/* etainv_op_word_maps with the two arguments the engine's launches also vary: row_sel (0 = source cond row, 1 = target cond row of the store) and
+ * layer_mask (bit l = stored layer l; see etainv_maps_word_maps_ex) */
+int etainv_op_word_maps_ex(const float* maps_acc, int n_layers, int n_img_cap, int heads, int res, int L, int n_img,
+                           const int32_t* tokens, int n_tok, int steps_done, int row_sel, unsigned layer_mask, float* out,
+                           int accumulate, float scale, void* stream);
+/* The small kernels at the edges of the UNet call (tests/test_small_kernels_gpu.py).
+ * etainv_op_time_embedding: sinusoidal timestep embedding [rows][dim] (flip_sin_to_cos, freq_shift 0) of the HOST timesteps t_host [rows];
+ *   via_device = 0 passes them by value in the kernel arguments, 1 writes them to the device vector t_dev [rows] floats first and reads
+ *   them from there (the form a captured hipGraph replays; t_dev may be NULL when via_device == 0).
+ * etainv_op_silu: out = silu(x) over n elements (out == x allowed).  etainv_op_cast: dst = (dst_dtype) src over n elements.
+ * etainv_op_im2col_in: latent NCHW [n_lat][4][l][l] io_dtype -> [rows][l*l][64] dtype, k = tap * 4 + ci, columns 36..63 zero; row r reads
+ *   latent r % n_lat.
+ * etainv_op_pack_weight: src fp32 [rows][cols] -> dst dtype; mode 0 copy, 1 conv OIHW [rows = O][cols = I * taps] -> [O][tap][I], 2 GEGLU row
+ *   interleave, 5 conv_in [O][4][3][3] -> [O][64] (cols must be 36).  Modes 0, 1, 2: every element times `scale`, then (modes 0 / 2 only) times
+ *   colscale[column] (may be NULL), in fp32, before the one rounding to dtype.  Mode 5 takes neither: scale must be 1 and colscale NULL.
+ *   Refused: any other mode, cols % taps != 0 in mode 1, rows % 64 != 0 in mode 2. */
+int etainv_op_time_embedding(const int64_t* t_host, int rows, int dim, void* out, int dtype, int via_device, float* t_dev, void* stream);
+int etainv_op_silu(const void* x, void* out, int64_t n, int dtype, void* stream);
+int etainv_op_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, void* stream);
+int etainv_op_im2col_in(const void* latent, int io_dtype, int n_lat, int rows, int l, void* out, int dtype, void* stream);
+int etainv_op_pack_weight(const float* src, void* dst, int64_t rows, int64_t cols, int mode, int taps, float scale, const float* colscale,
+                          int dtype, void* stream);
+/* etainv_op_gemm with an fp32 result [m][n]: the one GEMM of all time-embedding projections (ResnetBlock2D.time_emb_proj, n = 20160) */
+int etainv_op_gemm_f32out(const void* a, const void* w, const float* bias, float* out_f32, int m, int n, int k, int dtype, void* stream);
+/* etainv_op_conv3x3 whose time row is read as the UNet reads it: row i of rowvec starts at rowvec + i * rowvec_stride (a column block of that matrix) */
+int etainv_op_conv3x3_rv(const void* x_nhwc, const void* x2_nhwc, int c1, int c2, const void* w_okkc, const void* bias,
+                         const float* rowvec, int rowvec_stride, const void* residual, void* out, int b, int h, int wd, int cout,
+                         int stride, int upsample, int taps, int dtype, void* stream);
+/* GroupNorm (no activation) folded into the 1x1 conv behind it (Transformer2DModel.norm -> proj_in): stats [b][groups] (mean, rstd) pairs ->
+ * wb [b][n][k] = W rstd gamma (compute dtype), cb [b][n] = W (beta - mean rstd gamma) + bias; etainv_op_gemm_per_image then multiplies the hw rows
+ * of image i by wb[i] and adds cb[i] (hw must be a multiple of the kernel's M tile, else an error). */
+int etainv_op_gn_fold(const float* w, const float* gamma, const float* beta, const float* bias, const float* stats, int groups, int b, int n,
+                      int k, void* wb_out, float* cb_out, int dtype, void* stream);
+int etainv_op_gemm_per_image(const void* a, const void* wb, const float* cb, const void* residual, void* out, int b, int hw, int n, int k,
+                             int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
