@@ -2,6 +2,9 @@
 //   cfg_combine        eta_inversion.py:328
 //   ddim_step          scheduling_ddim_inverse.py:94-98
 //   eta_backward_step  eta_inversion.py:207-273, 296-317, 330-375 fused (2 launches, no host sync)
+//   edict_couple / edict_mix / edict_couple_mix   edict_inversion.py:144-179, 194-222 (scheduler steps), 317-338 (sync_latent_pair)
+#include <cmath>
+
 #include "common.h"
 
 namespace etainv {
@@ -183,9 +186,111 @@ __global__ void lincomb3_kernel(const T* __restrict__ x, float a, const T* __res
   }
 }
 
+// ---- EDICT (coupled latent pair).  Every product-sum is an explicit fmaf so that the fused kernel rounds exactly like the two it replaces
+// (nothing is left for the compiler to contract differently in one place than in the other).
+//   guided noise   eps = u + g (c - u)            (u == NULL: eps = c)
+//   coupled step   v   = a base + b eps           (a, b: host scalars of EdictScheduler.step / EdictSchedulerInverse.step)
+//   mix            x'  = p x + (1-p) y,  y' = (1-p) x' + p y;   inverse: y' = (y - (1-p) x) / p,  x' = (x - (1-p) y') / p
+__device__ __forceinline__ float edict_eps(float u, float c, float g) { return fmaf(g, c - u, u); }
+__device__ __forceinline__ float edict_step(float base, float eps, float a, float b) { return fmaf(b, eps, a * base); }
+__device__ __forceinline__ void edict_mix_fwd(float& x, float& y, float p, float q) {
+  x = fmaf(p, x, q * y);
+  y = fmaf(p, y, q * x);
+}
+__device__ __forceinline__ void edict_mix_inv(float& x, float& y, float p, float q) {
+  y = fmaf(-q, x, y) / p;
+  x = fmaf(-q, y, x) / p;
+}
+
+template <typename T>
+__global__ void edict_couple_kernel(const T* base, const T* __restrict__ eps_u, const T* __restrict__ eps_c, float g, float a, float b,
+                                    T* out, int64_t n) {   // (out may alias base: element i is read before it is written, by the same thread)
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) {
+    const float c = to_f32(eps_c[i]);
+    const float eps = eps_u ? edict_eps(to_f32(eps_u[i]), c, g) : c;
+    out[i] = from_f32<T>(edict_step(to_f32(base[i]), eps, a, b));
+  }
+}
+
+template <typename T>
+__global__ void edict_mix_kernel(T* __restrict__ x, T* __restrict__ y, float p, int inverse, int64_t n) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const float q = 1.f - p;
+  for (; i < n; i += stride) {
+    float xv = to_f32(x[i]), yv = to_f32(y[i]);
+    if (inverse) edict_mix_inv(xv, yv, p, q);
+    else edict_mix_fwd(xv, yv, p, q);
+    x[i] = from_f32<T>(xv);
+    y[i] = from_f32<T>(yv);
+  }
+}
+
+template <typename T>
+__global__ void edict_couple_mix_kernel(T* __restrict__ x, T* __restrict__ y, int base_is_y, const T* __restrict__ eps_u,
+                                        const T* __restrict__ eps_c, float g, float a, float b, float p, int64_t n) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const float q = 1.f - p;
+  for (; i < n; i += stride) {
+    float xv = to_f32(x[i]), yv = to_f32(y[i]);
+    const float c = to_f32(eps_c[i]);
+    const float eps = eps_u ? edict_eps(to_f32(eps_u[i]), c, g) : c;
+    if (base_is_y) yv = edict_step(yv, eps, a, b);
+    else xv = edict_step(xv, eps, a, b);
+    edict_mix_fwd(xv, yv, p, q);
+    x[i] = from_f32<T>(xv);
+    y[i] = from_f32<T>(yv);
+  }
+}
+
 }  // namespace etainv
 
 using namespace etainv;
+
+extern "C" int etainv_edict_couple(const void* base, const void* eps_u, const void* eps_c, float g, float a, float b, void* out, int64_t n,
+                                   int io_dtype, void* stream) {
+  ETAINV_CHECK(base && eps_c && out && n >= 0, "null pointer or negative size");
+  ETAINV_CHECK(std::isfinite(g) && std::isfinite(a) && std::isfinite(b), "edict_couple: g, a, b must be finite");
+  if (n == 0) return 0;
+  const int grid = (int)std::min<int64_t>(cdiv(n, 256), 2048);
+  ETAINV_DISPATCH_DTYPE(io_dtype, T,
+                        hipLaunchKernelGGL(edict_couple_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)base,
+                                           (const T*)eps_u, (const T*)eps_c, g, a, b, (T*)out, n));
+  ETAINV_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int etainv_edict_mix(void* x, void* y, float p, int inverse, int64_t n, int io_dtype, void* stream) {
+  ETAINV_CHECK(x && y && n >= 0, "null pointer or negative size");
+  ETAINV_CHECK(x != y, "edict_mix: x and y are the two latents of a pair, not one buffer");
+  ETAINV_CHECK(p > 0.f && p <= 1.f, "edict_mix: mix weight p must be in (0, 1]");
+  ETAINV_CHECK(inverse == 0 || inverse == 1, "edict_mix: inverse must be 0 or 1");
+  if (n == 0) return 0;
+  const int grid = (int)std::min<int64_t>(cdiv(n, 256), 2048);
+  ETAINV_DISPATCH_DTYPE(io_dtype, T,
+                        hipLaunchKernelGGL(edict_mix_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (T*)x, (T*)y, p, inverse, n));
+  ETAINV_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int etainv_edict_couple_mix(void* x, void* y, int base_is_y, const void* eps_u, const void* eps_c, float g, float a, float b, float p,
+                                       int64_t n, int io_dtype, void* stream) {
+  ETAINV_CHECK(x && y && eps_c && n >= 0, "null pointer or negative size");
+  ETAINV_CHECK(x != y, "edict_couple_mix: x and y are the two latents of a pair, not one buffer");
+  ETAINV_CHECK(base_is_y == 0 || base_is_y == 1, "edict_couple_mix: base_is_y must be 0 or 1");
+  ETAINV_CHECK(std::isfinite(g) && std::isfinite(a) && std::isfinite(b), "edict_couple_mix: g, a, b must be finite");
+  ETAINV_CHECK(p > 0.f && p <= 1.f, "edict_couple_mix: mix weight p must be in (0, 1]");
+  if (n == 0) return 0;
+  const int grid = (int)std::min<int64_t>(cdiv(n, 256), 2048);
+  ETAINV_DISPATCH_DTYPE(io_dtype, T,
+                        hipLaunchKernelGGL(edict_couple_mix_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (T*)x, (T*)y, base_is_y,
+                                           (const T*)eps_u, (const T*)eps_c, g, a, b, p, n));
+  ETAINV_LAUNCH_CHECK();
+  return 0;
+}
 
 extern "C" int etainv_lincomb3(const void* x, float a, const void* y, float b, const void* z, float c, void* out, int64_t n, int io_dtype,
                                void* stream) {

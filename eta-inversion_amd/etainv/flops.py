@@ -75,3 +75,11 @@ def unet_tflop(L):
 def exit_share(L, block):
     """share of a sample-forward's MACs a row has run when it leaves after transformer block `block`"""
     return unet_macs(L, block) / unet_macs(L)
+
+
+def edict_unet_rows(steps_fwd, steps_bwd, n_img, n_prompts, g_fwd=3.0, g_bwd=3.0):
+    """UNet sample-forwards of an EDICT inversion + backward pass (etainv.pipeline.EdictLoop): every step updates both members of the latent
+    pair, each from a UNet call on the other -- twice the rows of a plain DDIM step (`diffinv`) per step.  A call runs the uncond and the cond
+    row of each latent unless the guidance scale is 0 or 1 (one of them)."""
+    per_latent = lambda g: 1 if g in (0, 1) else 2
+    return 2 * steps_fwd * n_img * per_latent(g_fwd) + 2 * steps_bwd * n_img * n_prompts * per_latent(g_bwd)

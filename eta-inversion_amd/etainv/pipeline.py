@@ -8,6 +8,7 @@ Replaces, for B independent (source, target) pairs at once (the reference handle
   EtaInversion.invert (per-step word maps + mean)               reference modules/inversion/eta_inversion.py:36-49,378-404
   EtaInversion.diffusion_backward / predict_step_backward       reference modules/inversion/eta_inversion.py:207-294
   DiffusionInversion.sample batch layout                        reference modules/inversion/diffusion_inversion.py:462-528
+  EdictInversion.predict_step_forward / predict_step_backward   reference modules/inversion/edict_inversion.py:393-420 (EdictLoop)
 """
 import ctypes as C
 import os
@@ -17,7 +18,7 @@ import torch
 
 from . import _capi
 from .engine import AttnControl
-from .flops import exit_share
+from .flops import edict_unet_rows, exit_share
 
 NUM_TRAIN = 1000
 
@@ -338,3 +339,129 @@ def noise_table(S, n, L, seed=0, device="cuda"):
     """CPU torch generator, reseeded per image like the reference (eta_inversion.py:276): one table for all images."""
     g = torch.Generator().manual_seed(seed)
     return torch.stack([torch.randn((n, 1, 4, L, L), generator=g) for _ in range(S)]).reshape(S, n, 4, L, L).to(device)
+
+
+# ---------------------------------------------------------------- EDICT host tables (reference modules/inversion/edict_inversion.py)
+def edict_timesteps(S, init_image_strength=1.0):
+    """(forward, backward) timesteps that run: the scheduler's leading-spaced S timesteps with the t_limit = S - int(S strength) noisiest
+    ones cut off both ways (:258,422-428)"""
+    t_bwd = (np.arange(S) * (NUM_TRAIN // S))[::-1].astype(np.int64)
+    t_limit = S - int(S * init_image_strength)
+    return t_bwd[::-1][:S - t_limit].copy(), t_bwd[t_limit:].copy()
+
+
+def edict_alpha(ac, final, t):
+    """get_alpha_and_beta (:82-111) on the fp32 table `ac` (torch): a long timestep indexes it; the float `t - 1000 / S` takes
+    final_alpha_cumprod below 0 and otherwise `low * rem + high * (1 - rem)` -- the reference's weights, reversed as they are"""
+    if t.dtype == torch.long:
+        return ac[t]
+    if t < 0:
+        return final
+    low, high = t.floor().long(), t.ceil().long()
+    rem = t - low
+    return ac[low] * rem + ac[high] * (1 - rem)
+
+
+def edict_coefficients(ac, final, t, S, inverse):
+    """(a, b) of x' = a x + b eps at timestep t, in fp32 tensor arithmetic like the reference's scheduler steps (:157-173 denoising, :207-222
+    inversion): q = sqrt(abar_t / abar_prev), prev = t - 1000 / S as a float"""
+    t = torch.as_tensor(int(t), dtype=torch.long)
+    prev = t - NUM_TRAIN / S
+    a_t, a_p = edict_alpha(ac, final, t), edict_alpha(ac, final, prev)
+    q = (a_t / a_p) ** 0.5
+    if inverse:
+        a, b = q, (1 - a_t) ** 0.5 - q * (1 - a_p) ** 0.5
+    else:
+        a = 1.0 / q
+        b = (1 - a_p) ** 0.5 - a * (1 - a_t) ** 0.5
+    return float(a), float(b)
+
+
+def edict_order(i, S, is_fwd, leapfrog_steps=True):
+    """iter_latent_pair (:288-315): the pair member updated first and second at step index i of the (truncated) timestep list; S is the full
+    number of scheduler timesteps"""
+    off = ((S - i) % 2 if leapfrog_steps else 1) if is_fwd else i % 2
+    return off, 1 - off
+
+
+class EdictLoop:
+    """EDICT (coupled latent pair) for B images at once: per step two UNet calls, the second on the first's output, and the fused
+    etainv_edict_* kernels between them.  All tables (timesteps, coefficients, update order) are host scalars computed once."""
+
+    def __init__(self, engine, S=50, guidance_scale_fwd=3.0, guidance_scale_bwd=3.0, mix_weight=0.93, leapfrog_steps=True, init_image_strength=1.0):
+        if not 0.0 < float(mix_weight) <= 1.0:
+            raise ValueError(f"mix_weight must be in (0, 1], got {mix_weight}")
+        self.e, self.S, self.L = engine, S, engine.L
+        self.g_fwd, self.g_bwd, self.p = float(guidance_scale_fwd), float(guidance_scale_bwd), float(mix_weight)
+        self.leapfrog_steps, self.init_image_strength = leapfrog_steps, init_image_strength
+        self.t_fwd, self.t_bwd = edict_timesteps(S, init_image_strength)
+        ac = torch.as_tensor(alphas_cumprod().astype(np.float32))
+        self.coef_fwd = [edict_coefficients(ac, ac[0], t, S, True) for t in self.t_fwd]
+        self.coef_bwd = [edict_coefficients(ac, ac[0], t, S, False) for t in self.t_bwd]
+        self.order_fwd = [edict_order(i, S, True, leapfrog_steps) for i in range(len(self.t_fwd))]
+        self.order_bwd = [edict_order(i, S, False) for i in range(len(self.t_bwd))]
+        self.rows_executed = 0
+        self.lib = engine.lib
+
+    @staticmethod
+    def _rows(ctx_u, ctx_c, g):
+        """context rows of predict_noise (diffusion_inversion.py:263-286): scale 0 / 1 run one half, no guidance arithmetic"""
+        if g in (0.0, 1.0):
+            return (ctx_c if g == 1.0 else ctx_u).contiguous().float(), False
+        return torch.cat([ctx_u, ctx_c]).contiguous().float(), True
+
+    def invert(self, z0, ctx_src, guidance_scale_fwd=None):
+        """z0 (B,4,L,L) fp32; ctx_src (B,2,77,768) = [uncond, cond] per image.  Returns the pair trajectory (S'+1,2,B,4,L,L): [0] = two copies of z0."""
+        e, L = self.e, self.L
+        g = float(guidance_scale_fwd or self.g_fwd)
+        B, dev = z0.shape[0], z0.device
+        n_steps = len(self.t_fwd)
+        lat = torch.empty(n_steps + 1, 2, B, 4, L, L, dtype=torch.float32, device=dev)
+        lat[0, 0].copy_(z0)
+        lat[0, 1].copy_(z0)
+        ctx, guided = self._rows(ctx_src[:, 0], ctx_src[:, 1], g)
+        rows = ctx.shape[0]
+        eps_all = torch.empty(rows, 4, L, L, dtype=torch.float32, device=dev)
+        eps_u, eps_c = (_capi.ptr(eps_all[:B]), _capi.ptr(eps_all[B:])) if guided else (None, _capi.ptr(eps_all))
+        n = B * 4 * L * L
+        st = _capi.stream_ptr()
+        with e.cached_context():
+            for j, t in enumerate(self.t_fwd):
+                pair = lat[j + 1]
+                pair.copy_(lat[j])
+                _capi.check(self.lib.etainv_edict_mix(_capi.ptr(pair[0]), _capi.ptr(pair[1]), self.p, 1, n, _capi.F32, st))
+                a, b = self.coef_fwd[j]
+                for k in self.order_fwd[j]:
+                    e.unet(pair[1 - k], int(t), ctx, None, out=eps_all)
+                    self.rows_executed += rows
+                    _capi.check(self.lib.etainv_edict_couple(_capi.ptr(pair[k]), eps_u, eps_c, g, a, b, _capi.ptr(pair[k]), n, _capi.F32, st))
+        return {"latents": lat}
+
+    def sample(self, inv, ctx_list):
+        """inv: result of `invert`; ctx_list: one (B,2,77,768) context per prompt -- [src, tgt] gives UNet rows [u_src x B, u_tgt x B, c_src x B,
+        c_tgt x B] over the latents [src x B, tgt x B], one prompt gives [u x B, c x B].  Returns the final pair (2, n B, 4, L, L)."""
+        e, L = self.e, self.L
+        last = inv["latents"][-1]
+        n_p, B, dev = len(ctx_list), last.shape[1], last.device
+        pair = torch.stack([torch.cat([last[m]] * n_p) for m in range(2)]).contiguous()
+        ctx, guided = self._rows(torch.cat([c[:, 0] for c in ctx_list]), torch.cat([c[:, 1] for c in ctx_list]), self.g_bwd)
+        rows, nb = ctx.shape[0], n_p * B
+        eps_all = torch.empty(rows, 4, L, L, dtype=torch.float32, device=dev)
+        eps_u, eps_c = (_capi.ptr(eps_all[:nb]), _capi.ptr(eps_all[nb:])) if guided else (None, _capi.ptr(eps_all))
+        n = nb * 4 * L * L
+        st = _capi.stream_ptr()
+        x, y = _capi.ptr(pair[0]), _capi.ptr(pair[1])
+        with e.cached_context():
+            for i, t in enumerate(self.t_bwd):
+                a, b = self.coef_bwd[i]
+                k1, k2 = self.order_bwd[i]
+                e.unet(pair[1 - k1], int(t), ctx, None, out=eps_all)
+                _capi.check(self.lib.etainv_edict_couple(_capi.ptr(pair[k1]), eps_u, eps_c, self.g_bwd, a, b, _capi.ptr(pair[k1]), n, _capi.F32, st))
+                e.unet(pair[1 - k2], int(t), ctx, None, out=eps_all)
+                _capi.check(self.lib.etainv_edict_couple_mix(x, y, k2, eps_u, eps_c, self.g_bwd, a, b, self.p, n, _capi.F32, st))
+                self.rows_executed += 2 * rows
+        return pair
+
+    def expected_rows(self, B, n_prompts, guidance_scale_fwd=None):
+        """UNet sample-forwards of one invert + one sample (flops.edict_unet_rows)"""
+        return edict_unet_rows(len(self.t_fwd), len(self.t_bwd), B, n_prompts, float(guidance_scale_fwd or self.g_fwd), self.g_bwd)

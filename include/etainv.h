@@ -89,6 +89,22 @@ int etainv_eta_backward_step_ex(const void* x, const void* eps_all, float g, con
  * DPMSolverMultistepScheduler.step behind DiffusionInversion.step_backward, modules/inversion/diffusion_inversion.py:279-312) */
 int etainv_lincomb3(const void* x, float a, const void* y, float b, const void* z, float c, void* out, int64_t n, int io_dtype, void* stream);
 
+/* ---- EDICT (coupled latent pair; reference modules/inversion/edict_inversion.py)
+ * out = a * base + b * (eps_u + g * (eps_c - eps_u)): classifier-free guidance (DiffusionInversion.predict_noise) and the scheduler step of
+ * EdictScheduler.step (:144-179, eta = 0) / EdictSchedulerInverse.step (:194-222) in one pass.  a, b are the host scalars of that step
+ * (q = sqrt(abar_t / abar_prev); denoising: a = 1/q, b = sqrt(1-abar_prev) - sqrt(1-abar_t)/q; inversion: a = q,
+ * b = sqrt(1-abar_t) - q sqrt(1-abar_prev)).  eps_u == NULL: no guidance, eps = eps_c (the guidance 0 / 1 case of predict_noise).
+ * `out` may be `base`. */
+int etainv_edict_couple(const void* base, const void* eps_u, const void* eps_c, float g, float a, float b, void* out, int64_t n,
+                        int io_dtype, void* stream);
+/* sync_latent_pair (:317-338), in place on the pair, in the reference's order.  inverse == 0 (denoising): x <- p x + (1-p) y, then
+ * y <- (1-p) x_new + p y.  inverse == 1 (inversion): y <- (y - (1-p) x) / p, then x <- (x - (1-p) y_new) / p.  p in (0, 1]. */
+int etainv_edict_mix(void* x, void* y, float p, int inverse, int64_t n, int io_dtype, void* stream);
+/* tail of a denoising step (predict_step_backward :408-420): the second half-step's coupled update of x (base_is_y == 0) or y
+ * (base_is_y == 1) followed by the mix; bit for bit etainv_edict_couple then etainv_edict_mix(inverse = 0) with fp32 tensors. */
+int etainv_edict_couple_mix(void* x, void* y, int base_is_y, const void* eps_u, const void* eps_c, float g, float a, float b, float p,
+                            int64_t n, int io_dtype, void* stream);
+
 /* ---------------------------------------------------------------- engine */
 typedef struct etainv_engine etainv_engine_t;
 
