@@ -1218,9 +1218,18 @@ static int launch_cross_t(const void* q, const void* kv, void* out, int b, const
 }
 
 int launch_cross_attention_p(const void* q, const void* kv, void* out, int b, int d, const CrossParams& p, int dtype, hipStream_t s) {
-  if (dtype == ETAINV_F32) return launch_cross_attention_f32(q, kv, out, b, d, p, s);
-  ETAINV_CHECK(q && kv && out && b > 0, "bad arguments");
+  ETAINV_CHECK(q && kv && out && b > 0 && p.N > 0 && p.heads > 0, "bad arguments");
   ETAINV_CHECK(p.n_ctx >= 1 && p.n_ctx <= 77, "n_ctx must be in [1,77]");
+  ETAINV_CHECK(d == 40 || d == 80 || d == 160, "head_dim must be 40, 80 or 160");
+  // the kernels take every row's role, image and source row (b - n_img) from the layout: a row count that does not fit it reads rows that do not exist
+  ETAINV_CHECK(p.layout >= 0 && p.layout <= 3 && (p.layout == 0 || p.n_img >= 1), "cross-attention: layout 0..3, n_img >= 1");
+  ETAINV_CHECK(p.layout != 1 || b == p.n_img || b == 2 * p.n_img, "cross-attention store layout [u, c] x n_img: n_img or 2*n_img rows");
+  ETAINV_CHECK(p.layout != 2 || ((p.first_row == 0 || p.first_row == p.n_img) && b + p.first_row == 4 * p.n_img),
+               "cross-attention prompt-to-prompt layout: rows [first_row, 4*n_img) of [u_s,u_t,c_s,c_t] x n_img, first_row 0 or n_img");
+  ETAINV_CHECK(p.layout != 3 || b == 2 * p.n_img || b == 3 * p.n_img, "cross-attention layout [u_t, c_t, c_s] x n_img: 3*n_img rows, or 2*n_img once the source rows have left");
+  ETAINV_CHECK(!p.edit || p.cross_alpha, "cross-attention edit without cross_alpha");
+  ETAINV_CHECK(p.map_layer < 0 || (p.maps_acc && p.n_img <= p.n_img_cap), "cross-attention map store: maps_acc missing or n_img > n_img_cap");
+  if (dtype == ETAINV_F32) return launch_cross_attention_f32(q, kv, out, b, d, p, s);
   ETAINV_DISPATCH_HALF(dtype, T, switch (d) {
     case 40: return launch_cross_t<T, 40>(q, kv, out, b, p, s);
     case 80: return launch_cross_t<T, 80>(q, kv, out, b, p, s);

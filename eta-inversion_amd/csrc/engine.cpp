@@ -700,18 +700,8 @@ struct Fwd {
     cp.rows = rows;
     cp.n_img_cap = e->max_img;
     cp.maps_acc = e->maps_cur;
-    if (ctrl && (ctrl->mode == ETAINV_ATTN_PTP || ctrl->mode == ETAINV_ATTN_STORE)) {
-      cp.n_img = ctrl->n_img;
-      cp.layout = ctrl->mode == ETAINV_ATTN_PTP ? (ctrl->src_exit_block ? 3 : 2) : 1;   // 3: rows [u_t, c_t, c_s] (cond source rows leave early)
-      cp.first_row = ctrl->mode == ETAINV_ATTN_PTP ? ctrl->first_row : 0;
-      if (ctrl->mode == ETAINV_ATTN_PTP && ctrl->cross_alpha && (ctrl->mapper || ctrl->replace_mat)) {
-        cp.edit = 1;
-        cp.mapper = ctrl->mapper;
-        cp.alphas = ctrl->alphas;
-        cp.replace_mat = ctrl->replace_mat;
-        cp.equalizer = ctrl->equalizer;
-        cp.cross_alpha = ctrl->cross_alpha;
-      }
+    cross_params_from_ctrl(cp, ctrl);
+    if (cp.layout) {
       const int res = e->L / e->map_div;
       if (ctrl->store_maps && hw == res * res) {
         // the five (L/4)^2-token cross layers: transformer blocks 4,5 (down) and 7,8,9 (up); (L/2)^2: 2,3 and 10,11,12; (L/8)^2: the mid block 6
@@ -1484,20 +1474,8 @@ extern "C" int etainv_op_cross_attention(const void* q, const void* kv, void* ou
   cp.rows = b;
   cp.n_img_cap = n_img_cap;
   cp.maps_acc = maps_acc;
-  if (ctrl && (ctrl->mode == ETAINV_ATTN_PTP || ctrl->mode == ETAINV_ATTN_STORE)) {
-    cp.n_img = ctrl->n_img;
-    cp.layout = ctrl->mode == ETAINV_ATTN_PTP ? 2 : 1;
-    cp.first_row = ctrl->mode == ETAINV_ATTN_PTP ? ctrl->first_row : 0;
-    if (ctrl->mode == ETAINV_ATTN_PTP && ctrl->cross_alpha && (ctrl->mapper || ctrl->replace_mat)) {
-      cp.edit = 1;
-      cp.mapper = ctrl->mapper;
-      cp.alphas = ctrl->alphas;
-      cp.replace_mat = ctrl->replace_mat;
-      cp.equalizer = ctrl->equalizer;
-      cp.cross_alpha = ctrl->cross_alpha;
-    }
-    if (ctrl->store_maps && maps_acc) cp.map_layer = map_layer;
-  }
+  cross_params_from_ctrl(cp, ctrl);
+  if (cp.layout && ctrl->store_maps && map_layer >= 0) cp.map_layer = map_layer;   // (without maps_acc: the launcher's refusal, not a silent loss of maps)
   return launch_cross_attention_p(q, kv, out, b, d, cp, dtype, (hipStream_t)stream);
 }
 

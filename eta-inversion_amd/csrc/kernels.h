@@ -138,6 +138,25 @@ struct CrossParams {
   float* maps_acc = nullptr;
   int xcd_gx = 0;      // > 0: 1-D grid with the heads of one (row, query range) on one XCD; the value = query-block lanes per (row, head) (attention.hip)
 };
+// What an etainv_attn_ctrl means for a cross-attention launch: row layout, image count, first row and the prompt-to-prompt edit tables.  The one
+// definition for the UNet's transformer blocks and for etainv_op_cross_attention (the map store -- map_layer, maps_acc, n_img_cap -- is the caller's).
+inline void cross_params_from_ctrl(CrossParams& cp, const etainv_attn_ctrl* ctrl) {
+  if (!ctrl || (ctrl->mode != ETAINV_ATTN_PTP && ctrl->mode != ETAINV_ATTN_STORE)) return;
+  const bool ptp = ctrl->mode == ETAINV_ATTN_PTP;
+  cp.n_img = ctrl->n_img;
+  cp.layout = ptp ? (ctrl->src_exit_block ? 3 : 2) : 1;   // 3: rows [u_t, c_t, c_s] (cond source rows leave early)
+  cp.first_row = ptp ? ctrl->first_row : 0;
+  if (ptp && (ctrl->mapper || ctrl->replace_mat)) {   // (without cross_alpha: the launcher's refusal, not a silently skipped edit)
+    cp.edit = 1;
+    cp.mapper = ctrl->mapper;
+    cp.alphas = ctrl->alphas;
+    cp.replace_mat = ctrl->replace_mat;
+    cp.equalizer = ctrl->equalizer;
+    cp.cross_alpha = ctrl->cross_alpha;
+  }
+}
+// Refuses (before any launch, 16-bit and fp32 alike) a row count that does not fit the layout -- layout 1: b in {n_img, 2 n_img}; layout 2: first_row in
+// {0, n_img} and b + first_row == 4 n_img; layout 3: b in {2 n_img, 3 n_img} --, an edit without cross_alpha, a store without maps_acc or with n_img > n_img_cap.
 int launch_cross_attention_p(const void* q, const void* kv, void* out, int b, int d, const CrossParams& p, int dtype, hipStream_t s);
 
 // ---- misc.hip

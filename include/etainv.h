@@ -325,6 +325,10 @@ int etainv_op_self_attention(const void* qkv, void* out, int b, int n, int heads
  * head_major: qkv holds three planes [q|k|v][b][heads][n][d] instead of rows [b][n][3 heads d] (head_dim 40 / 80, 16-bit types; else an error). */
 int etainv_op_self_attention_ex(const void* qkv, void* out, int b, int n, int heads, int d, int mode, int n_img,
                                 int q_prescaled, int first_row, int head_major, int dtype, void* stream);
+/* q [b][n][heads d], kv [b][n_ctx][2 heads d] (1 <= n_ctx <= 77), head_dim 40 / 80 / 160.  ctrl as in the UNet call: STORE = rows [u, c] x n_img or [c] x n_img;
+ * PTP = rows [first_row, 4 n_img) of [u_s, u_t, c_s, c_t] x n_img, or, with src_exit_block != 0, rows [u_t, c_t, c_s] x n_img / [u_t, c_t] x n_img (store only).
+ * mapper or replace_mat asks for the edit (needs cross_alpha); store_maps with map_layer >= 0 accumulates into maps_acc [layers][n_img_cap][2][heads][n][77].
+ * A row count that does not fit the layout, an edit without cross_alpha and a store without maps_acc or with n_img > n_img_cap are errors; nothing is launched. */
 int etainv_op_cross_attention(const void* q, const void* kv, void* out, int b, int n, int heads, int d,
                               int n_ctx, const etainv_attn_ctrl* ctrl, int map_layer, int n_img_cap,
                               float* maps_acc, int dtype, void* stream);

@@ -104,6 +104,20 @@ def test_argument_errors_are_reported_not_crashed():
     assert b"null" in lib.etainv_last_error()
     with pytest.raises(_capi.EtainvError):
         _capi.check(lib.etainv_ddim_step(None, None, 0.5, 0.5, None, 4, _capi.F32, None))
+    # cross-attention: a row count that does not fit the layout, an edit or a store without its tables, a context or head_dim the kernels do not have -- refused by
+    # the launcher before it touches a pointer, on the 16-bit and the fp32 path (the same list, with real tensors: tests/test_cross_attention_gpu.py)
+    import ctypes as C
+    from tests import cross_attention_ref as XR
+    buf = C.create_string_buffer(64)
+    p = C.addressof(buf)
+    for dtype in (_capi.F16, _capi.BF16, _capi.F32):
+        for name, over, fragment in XR.REFUSALS:
+            a = dict(XR.REFUSAL_BASE, **over)
+            ctrl = _capi.AttnCtrl(mode=_capi.ATTN_PTP if a["mode"] == "ptp" else _capi.ATTN_STORE, n_img=a["n_img"], store_maps=a["store"], mapper=p if a["mapper"] else None,
+                                  cross_alpha=p if a["cross_alpha"] else None, first_row=a["first_row"], src_exit_block=a["src_exit_block"])
+            st = lib.etainv_op_cross_attention(p, p, p, a["b"], 40, 8, a["d"], a["n_ctx"], C.byref(ctrl), 1, a["n_img_cap"], p if a["maps"] else None, dtype, None)
+            assert st != 0 and fragment.encode() in lib.etainv_last_error(), (name, dtype, st, lib.etainv_last_error())
+    assert lib.etainv_op_cross_attention(None, p, p, 8, 40, 8, 40, 77, None, -1, 1, None, _capi.F32, None) != 0 and b"bad arguments" in lib.etainv_last_error()
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU failure mode")

@@ -1005,7 +1005,8 @@ def _ptp_tables(n_img):
 def test_cross_attention_ptp_edit_and_store(capi, dtype, n, d):
     """Cross-attention with the fused Refine + Reweight edit on the cond target rows and AttentionStore accumulation,
     against the oracle's controller algebra (pinned by tests/golden/ptp_algebra.npz) on materialised probabilities.  Token counts of the 512^2 and 768^2
-    configurations; the bound holds per (row, head, 32-query block) as well as globally."""
+    configurations; the bound holds per (row, head, 32-query block) as well as globally.
+    (Its tables are 0 / 1 at step 0: fractional blend weights, Replace, layouts 1 and 3, short contexts and the store per element are in tests/test_cross_attention_gpu.py.)"""
     from oracle import ptp as optp
     lib = capi.load()
     n_img, heads = 2, 8
