@@ -112,7 +112,8 @@ __device__ __forceinline__ float max32(const f32x16 (&s)[2]) {
 }
 
 // mode: 0 plain; 1 ptp self-replace (cond target rows take Q,K of their source row); 2 masactrl (target rows
-// of both halves take K,V of their source row)
+// of both halves take K,V of their source row); 3 plug-and-play (rows [u_s, u_t, c_t] x n_img: the target rows take Q,K of the
+// uncond source row of their image, V stays their own)
 template <typename T, int D, bool XCD_REMAP, int QB, int OCC>
 __global__ void __launch_bounds__(256, OCC) self_attn40_kernel(const T* __restrict__ qkv, T* __restrict__ out, int N, int heads,
                                                                float q_scale, int mode, int n_img, int nqb, int first_row, int hm_rows) {
@@ -153,6 +154,7 @@ __global__ void __launch_bounds__(256, OCC) self_attn40_kernel(const T* __restri
       row_roles(b + first_row, n_img, half, role, img);   // (first_row: the call carries rows [first_row, 4 n_img) of the [u_s,u_t,c_s,c_t] layout)
       if (mode == 1 && half == 1 && role == 1) { bq = b - n_img; bk = b - n_img; }
       if (mode == 2 && role == 1) { bk = b - n_img; bv = b - n_img; }
+      if (mode == 3) { bq = img; bk = img; }   // pnp rows [u_s, u_t, c_t] x n_img (first_row == 0): img == b % n_img, the row itself for b < n_img
     }
   }
   const int q_base = qblk * (128 * QB) + wid * (32 * QB);
@@ -438,7 +440,9 @@ __global__ void __launch_bounds__(256, OCC) self_attn40_kernel(const T* __restri
 // head_dim 80 (the (L/2)^2 level; 24 MFMAs per unit, matrix-bound) runs the same code with QB = 2, NW = 4 and items of 256 queries: 0.443 against 0.491 ms at N = 1024 x 128 rows.
 // Requirements (persistent_self_ok, self_attn_route.h): N a multiple of the item's queries and of 256 (tiles: a multiple of 4, >= 16), the QKV tensor below 4 GB (one buffer descriptor, 32-bit
 // scalar offsets), >= 2 items per CU.  ETAINV_A40_PERSIST=0 / ETAINV_A80_PERSIST=0: self_attn40_kernel as before.
-template <typename T, int D, int QB, int NW>
+// PNP: the plug-and-play row coupling (mode 3) as an instantiation of its own -- this kernel holds 256 registers with the scalar file full, and a fourth
+// mode decoded at run time moved the allocation of the modes 0..2 code (spilled scalars at head_dim 80); with PNP = false nothing of it is compiled.
+template <typename T, int D, int QB, int NW, bool PNP = false>
 __global__ void __launch_bounds__(64 * NW, 1) self_attn40q_kernel(const T* __restrict__ qkv, T* __restrict__ out, int N, int heads, float q_scale, int mode, int n_img,
                                                               int nqb, int n_items, int first_row, int hm_rows, int xcd_remap, unsigned qkv_bytes) {
   typedef typename Frag<T>::v8 v8;
@@ -521,7 +525,10 @@ __global__ void __launch_bounds__(64 * NW, 1) self_attn40q_kernel(const T* __res
       b = t / heads;
     }
     int bq = b, bk = b, bv = b;
-    if (mode != 0) {
+    if constexpr (PNP) {   // mode 3, rows [u_s, u_t, c_t] x n_img: Q, K of the u_s row of the image (the row itself for b < n_img), V the row's own
+      bq = b % n_img;
+      bk = bq;
+    } else if (mode != 0) {
       int half, role, img;
       if (first_row < 0) {
         if (mode == 1 && b / n_img == 1) { bq = b + n_img; bk = b + n_img; }
@@ -1128,12 +1135,17 @@ static int launch_self40q(const void* qkv, void* out, int b, int n, int heads, i
   const int remap = ((b * heads) % 8) == 0;
   const float q_scale = q_prescaled ? 1.0f : (1.0f / sqrtf((float)D)) * 1.4426950408889634f;
   constexpr size_t lds = (size_t)(4 * (A32<D>::KBUF + A32<D>::VBUF) + A32<D>::VBUF) * 2;   // four tile buffers + the zero image (90 / 112 KB at head_dim 40 / 80; one block per CU)
-  allow_dynamic_lds<&self_attn40q_kernel<T, D, QB, NW>>(lds);
+  allow_dynamic_lds<&self_attn40q_kernel<T, D, QB, NW, false>>(lds);
+  allow_dynamic_lds<&self_attn40q_kernel<T, D, QB, NW, true>>(lds);
   ProfScope prof(PROF_SELF_ATTN, 4.0 * (double)b * heads * (double)n * (double)n * D, s);
   const unsigned qkv_bytes = (unsigned)((int64_t)3 * b * n * heads * D * 2);
   const int grid = n_items < n_cu ? n_items / 8 * 8 : n_cu / 8 * 8;
-  hipLaunchKernelGGL((self_attn40q_kernel<T, D, QB, NW>), dim3(grid), dim3(64 * NW), lds, s, (const T*)qkv, (T*)out, n, heads, q_scale, mode, n_img, nqb, n_items, first_row, hm_rows, remap,
-                     qkv_bytes);
+  if (mode == 3)
+    hipLaunchKernelGGL((self_attn40q_kernel<T, D, QB, NW, true>), dim3(grid), dim3(64 * NW), lds, s, (const T*)qkv, (T*)out, n, heads, q_scale, mode, n_img, nqb, n_items, first_row, hm_rows,
+                       remap, qkv_bytes);
+  else
+    hipLaunchKernelGGL((self_attn40q_kernel<T, D, QB, NW, false>), dim3(grid), dim3(64 * NW), lds, s, (const T*)qkv, (T*)out, n, heads, q_scale, mode, n_img, nqb, n_items, first_row, hm_rows,
+                       remap, qkv_bytes);
   ETAINV_LAUNCH_CHECK();
   return 0;
 }
@@ -1153,8 +1165,11 @@ int launch_self_attention_mode(const void* qkv, void* out, int b, int n, int hea
                                hipStream_t s, int q_prescaled, int first_row, int head_major) {
   ETAINV_CHECK((!head_major && !q_prescaled) || self_attn_prescaled_hm_ok(d, dtype), "head-major QKV planes / pre-scaled queries: head_dim 40 / 80 on the 16-bit kernels only");
   ETAINV_CHECK(qkv && out && b > 0 && n > 0, "bad arguments");
-  ETAINV_CHECK(mode == 0 || (n_img > 0 && ((first_row >= 0 && b + first_row == 4 * n_img && (first_row == 0 || (first_row == n_img && mode == 1))) ||
-                                           (first_row < 0 && b == 3 * n_img && mode == 1))),
+  ETAINV_CHECK(mode >= 0 && mode <= 3, "self-attention mode: 0 plain, 1 ptp self-replace, 2 masactrl, 3 plug-and-play");
+  // (a row count that does not fit the layout would read Q / K / V of batch rows that do not exist)
+  ETAINV_CHECK(mode != 3 || (n_img > 0 && first_row == 0 && b == 3 * n_img), "plug-and-play mode needs the 3*n_img layout [u_s, u_t, c_t] x n_img with first_row == 0");
+  ETAINV_CHECK(mode == 0 || mode == 3 || (n_img > 0 && ((first_row >= 0 && b + first_row == 4 * n_img && (first_row == 0 || (first_row == n_img && mode == 1))) ||
+                                                        (first_row < 0 && b == 3 * n_img && mode == 1))),
                "ptp / masactrl modes need the 4*n_img backward layout (ptp: optionally without its first n_img rows, or rows [u_t, c_t, c_s] with first_row < 0)");
   if (dtype == ETAINV_F32) return launch_self_attention_f32(qkv, out, b, n, heads, d, mode, n_img, s, first_row);
   ETAINV_CHECK(d == 40 || d == 80 || d == 160, "head_dim must be 40, 80 or 160");

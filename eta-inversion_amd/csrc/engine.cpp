@@ -605,11 +605,16 @@ struct Fwd {
     return run(p, gn_out);
   }
   // x = cat[x1 (c1), x2 (c2)] -> out
-  int resblock(const ResBlock& r, const void* x1, const void* x2, int c1, int c2, int side, void* out) {
+  // pnp_site: this is up_blocks[1].resnets[1], the one block of the plug-and-play feature injection
+  int resblock(const ResBlock& r, const void* x1, const void* x2, int c1, int c2, int side, void* out, bool pnp_site = false) {
     const int hw = side * side;
     if (groupnorm(x1, x2, c1, c2, r.n1, hw, 1e-5f, 1)) return 1;
     if (conv(e->gnbuf, r.conv1, e->h1, side, side, 1, 0, e->tprojbuf + r.tproj_off, nullptr)) return 1;
     if (groupnorm(e->h1, nullptr, r.cout, 0, r.n2, hw, 1e-5f, 1)) return 1;
+    // plug-and-play: conv2's output of the target rows is that of the u_s row of their image (pnp_utils.py conv_forward) -- conv2 is a function of its
+    // input row alone, so the substitution happens on its input; the shortcut / residual term below stays each row's own
+    if (pnp_site && ctrl && ctrl->mode == ETAINV_ATTN_PNP && ctrl->pnp_conv_active &&
+        launch_rows_broadcast(e->gnbuf, rows, ctrl->n_img, (int64_t)hw * r.cout, e->dt, s)) return 1;
     const void* residual = x1;
     if (r.shortcut.w) {
       if (gemm(x1, r.shortcut, e->scbuf, rows * hw, nullptr, 0, x2, c1, c2)) return 1;
@@ -629,6 +634,7 @@ struct Fwd {
       n_img = ctrl->n_img;
       if (ctrl->mode == ETAINV_ATTN_PTP && ctrl->self_replace_active && hw <= ctrl->self_max_tokens) mode = 1;
       if (ctrl->mode == ETAINV_ATTN_MASA && ctrl->masa_active && blk >= ctrl->masa_first_block) mode = 2;
+      if (ctrl->mode == ETAINV_ATTN_PNP && ctrl->pnp_qk_active && blk >= 8) mode = 3;   // up_blocks[1].attentions[1] onwards (pnp.py register_pnp)
     }
     const int all_rows = rows;
     if (self_rows <= 0 || self_rows >= all_rows || 2 * self_rows < all_rows || mode != 0 || e->gn_fold) self_rows = all_rows;   // (a row remap couples the halves: no sharing)
@@ -873,7 +879,7 @@ static int unet_graph(etainv_engine_t* e, const void* latent, int n_lat, const i
   std::string key;   // (built with std::to_string: no fixed buffer a long signature could truncate into another signature's key)
   for (const int v : {n_rows, n_lat, io_dtype, (int)t_pairs, (int)reuse, e->map_div, ctrl ? ctrl->mode : -1, ctrl ? ctrl->n_img : 0, ctrl ? ctrl->store_maps : 0,
                       ctrl ? ctrl->self_replace_active : 0, ctrl ? ctrl->self_max_tokens : 0, ctrl ? ctrl->masa_active : 0, ctrl ? ctrl->masa_first_block : 0,
-                      ctrl ? ctrl->first_row : 0, ctrl ? ctrl->src_exit_block : 0}) {
+                      ctrl ? ctrl->first_row : 0, ctrl ? ctrl->src_exit_block : 0, ctrl ? ctrl->pnp_qk_active : 0, ctrl ? ctrl->pnp_conv_active : 0}) {
     key += std::to_string(v);
     key += '.';
   }
@@ -962,6 +968,10 @@ static int unet_body(etainv_engine_t* e, const void* latent, int n_lat, const in
       ETAINV_CHECK(n_rows == 4 * ctrl->n_img - ctrl->first_row, "ptp / masactrl need 4*n_img UNet rows [u_s,u_t,c_s,c_t] (ptp with first_row = n_img: 3*n_img rows [u_t,c_s,c_t])");
     if (ctrl->mode == ETAINV_ATTN_STORE)
       ETAINV_CHECK(n_rows == 2 * ctrl->n_img || n_rows == ctrl->n_img, "store mode needs n_img or 2*n_img rows");
+    if (ctrl->mode == ETAINV_ATTN_PNP)
+      ETAINV_CHECK(n_rows == 3 * ctrl->n_img && n_lat == n_rows && !ctrl->store_maps && !ctrl->mapper && !ctrl->alphas && !ctrl->replace_mat && !ctrl->equalizer &&
+                       !ctrl->cross_alpha && ctrl->first_row == 0 && ctrl->src_exit_block == 0,
+                   "plug-and-play needs 3*n_img UNet rows [u_s,u_t,c_t] over as many latents [src,tgt,tgt], no map store, no tables, first_row == src_exit_block == 0");
   }
   hipStream_t s = (hipStream_t)stream;
   const int L = e->L;
@@ -1070,7 +1080,7 @@ static int unet_body(etainv_engine_t* e, const void* latent, int n_lat, const in
       const int skc = skip_c[sp];
       --sp;
       void* r_out = pick_tmp(e, h, nullptr);
-      if (f.resblock(e->res[ri++], h, sk, hc, skc, side, r_out)) return 1;
+      if (f.resblock(e->res[ri++], h, sk, hc, skc, side, r_out, /*pnp_site=*/i == 1 && j == 1)) return 1;
       h = r_out;
       hc = cout;
       if (i > 0) {
@@ -1461,6 +1471,10 @@ extern "C" int etainv_op_self_attention(const void* qkv, void* out, int b, int n
 extern "C" int etainv_op_self_attention_ex(const void* qkv, void* out, int b, int n, int heads, int d, int mode, int n_img, int q_prescaled, int first_row,
                                            int head_major, int dtype, void* stream) {
   return launch_self_attention_mode(qkv, out, b, n, heads, d, mode, n_img, dtype, (hipStream_t)stream, q_prescaled, first_row, head_major);
+}
+
+extern "C" int etainv_op_rows_broadcast(void* x, int rows, int n_src, int64_t row_elems, int dtype, void* stream) {
+  return launch_rows_broadcast(x, rows, n_src, row_elems, dtype, (hipStream_t)stream);
 }
 
 extern "C" int etainv_op_cross_attention(const void* q, const void* kv, void* out, int b, int n, int heads, int d, int n_ctx,

@@ -270,7 +270,7 @@ __global__ void __launch_bounds__(256) layernorm_f32_kernel(const float* __restr
 // One wave per 32 queries of one (batch row, head); S^T = K Q^T per 32-key block (keys -> accumulator registers, queries -> lanes), online
 // softmax per query (the two lanes of a query exchange through lane ^ 32), O^T += V^T P^T with each accumulator register of S^T used directly
 // as the B operand of one k = 2 step (lane half hh supplies key crow(r, hh): V^T is read in that order) -- no lane movement, no LDS for P.
-// mode 1 / 2: the prompt-to-prompt / MasaCtrl batch-row remaps of attention.hip (row_roles).
+// mode 1 / 2 / 3: the prompt-to-prompt / MasaCtrl / plug-and-play batch-row remaps of attention.hip (row_roles).
 template <int D>
 __global__ void __launch_bounds__(256) self_attn_f32_kernel(const float* __restrict__ qkv, float* __restrict__ out, int N, int heads, float scale_log2,
                                                             int mode, int n_img, int first_row) {
@@ -288,6 +288,7 @@ __global__ void __launch_bounds__(256) self_attn_f32_kernel(const float* __restr
       const int bl = b + first_row, half = bl / (2 * n_img), role = (bl / n_img) & 1;
       if (mode == 1 && half == 1 && role == 1) { bq = b - n_img; bk = b - n_img; }
       if (mode == 2 && role == 1) { bk = b - n_img; bv = b - n_img; }
+      if (mode == 3 && b >= n_img) { bq = b % n_img; bk = b % n_img; }   // pnp rows [u_s, u_t, c_t] x n_img
     }
   }
   const int query = blockIdx.x * 128 + wid * 32 + l31;
@@ -546,6 +547,7 @@ static int launch_self_f32_t(const void* qkv, void* out, int b, int n, int heads
 }
 
 int launch_self_attention_f32(const void* qkv, void* out, int b, int n, int heads, int d, int mode, int n_img, hipStream_t s, int first_row) {
+  ETAINV_CHECK(mode != 3 || (n_img > 0 && first_row == 0 && b == 3 * n_img), "plug-and-play mode needs the 3*n_img layout [u_s, u_t, c_t] x n_img with first_row == 0");
   switch (d) {
     case 40: return launch_self_f32_t<40>(qkv, out, b, n, heads, mode, n_img, s, first_row);
     case 80: return launch_self_f32_t<80>(qkv, out, b, n, heads, mode, n_img, s, first_row);

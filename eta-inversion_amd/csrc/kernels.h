@@ -178,6 +178,9 @@ int launch_pack_weight(const float* src, void* dst, int64_t rows, int64_t cols, 
 int launch_ln_fold(const float* w_src, const float* gamma, const float* beta, const float* bias_packed, int64_t rows, int64_t cols, int mode, float scale,
                    void* w_dst, float* s_dst, float* c_dst, int dtype, hipStream_t s);
 int launch_cast_f32(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, hipStream_t s);
+// activation [rows][row_elems], rows % n_src == 0: every row r >= n_src becomes a copy of row r % n_src (plug-and-play feature injection); a row must be
+// a whole number of 16-byte vectors
+int launch_rows_broadcast(void* x, int rows, int n_src, int64_t row_elems, int dtype, hipStream_t s);
 
 // ---- maps.hip
 int launch_word_maps(const float* maps_acc, int n_layers, int n_img_cap, int rows_per_img, int row_sel, int heads, int res, int L,

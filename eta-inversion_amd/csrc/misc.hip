@@ -284,6 +284,30 @@ int launch_ln_fold(const float* w_src, const float* gamma, const float* beta, co
   return 0;
 }
 
+// Plug-and-play feature injection (reference modules/utils/pnp_utils.py, register_conv_control_efficient): of an activation [rows][row_vecs] (16-byte
+// vectors) every row r >= n_src becomes a copy of row r % n_src.  Grid-stride over the destination vectors; source rows are only read.
+__global__ void __launch_bounds__(256) rows_broadcast_kernel(u32x4* x, int n_src, int64_t row_vecs, int64_t n_dst) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_dst; i += stride) {
+    const int64_t r = n_src + i / row_vecs, c = i - (i / row_vecs) * row_vecs;
+    x[r * row_vecs + c] = x[(r % n_src) * row_vecs + c];
+  }
+}
+
+int launch_rows_broadcast(void* x, int rows, int n_src, int64_t row_elems, int dtype, hipStream_t s) {
+  ETAINV_CHECK(x, "rows_broadcast: null activation");
+  ETAINV_CHECK(dtype == ETAINV_F32 || dtype == ETAINV_F16 || dtype == ETAINV_BF16, "rows_broadcast: dtype must be f32, f16 or bf16");
+  ETAINV_CHECK(rows > 0 && n_src > 0 && row_elems > 0 && rows % n_src == 0, "rows_broadcast: rows must be a positive multiple of n_src");
+  const int64_t row_bytes = row_elems * (dtype == ETAINV_F32 ? 4 : 2);
+  ETAINV_CHECK(row_bytes % 16 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0, "rows_broadcast: a row must be a whole number of aligned 16-byte vectors");
+  if (rows == n_src) return 0;   // nothing to overwrite
+  const int64_t row_vecs = row_bytes / 16, n_dst = (int64_t)(rows - n_src) * row_vecs;
+  const int64_t blocks = std::min<int64_t>((n_dst + 255) / 256, 2048);
+  hipLaunchKernelGGL(rows_broadcast_kernel, dim3((unsigned)blocks), dim3(256), 0, s, reinterpret_cast<u32x4*>(x), n_src, row_vecs, n_dst);
+  ETAINV_LAUNCH_CHECK();
+  return 0;
+}
+
 int launch_cast_f32(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, hipStream_t s) {
   ETAINV_DISPATCH_DTYPE(src_dtype, TS, ETAINV_DISPATCH_DTYPE(dst_dtype, TD,
       hipLaunchKernelGGL((cast_kernel<TS, TD>), dim3(cdiv(n, 256)), dim3(256), 0, s, (const TS*)src, (TD*)dst, n)));

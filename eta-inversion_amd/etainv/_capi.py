@@ -5,7 +5,7 @@ import os
 from pathlib import Path
 
 F32, F16, BF16 = 0, 1, 2
-ATTN_PLAIN, ATTN_STORE, ATTN_PTP, ATTN_MASA = 0, 1, 2, 3
+ATTN_PLAIN, ATTN_STORE, ATTN_PTP, ATTN_MASA, ATTN_PNP = 0, 1, 2, 3, 4
 
 _LIB_PATH = Path(__file__).resolve().parent / "lib" / "libetainv_hip.so"
 
@@ -24,7 +24,7 @@ class AttnCtrl(C.Structure):
                 ("mapper", C.c_void_p), ("alphas", C.c_void_p), ("replace_mat", C.c_void_p), ("equalizer", C.c_void_p),
                 ("cross_alpha", C.c_void_p),
                 ("self_replace_active", C.c_int), ("self_max_tokens", C.c_int),
-                ("masa_active", C.c_int), ("masa_first_block", C.c_int), ("first_row", C.c_int), ("src_exit_block", C.c_int), ("reserved", C.c_int * 2)]
+                ("masa_active", C.c_int), ("masa_first_block", C.c_int), ("first_row", C.c_int), ("src_exit_block", C.c_int), ("pnp_qk_active", C.c_int), ("pnp_conv_active", C.c_int)]
 
 
 _p, _i, _f, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_int64
@@ -101,6 +101,7 @@ SIGNATURES = {
     "etainv_op_conv3x3_rv": [_p, _p, _i, _i, _p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "etainv_op_gn_fold": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _i, _p],
     "etainv_op_gemm_per_image": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
+    "etainv_op_rows_broadcast": [_p, _i, _i, _i64, _i, _p],
 }
 _RESTYPES = {"etainv_last_error": C.c_char_p, "etainv_engine_workspace_bytes": _i64, "etainv_engine_weight_bytes": _i64}
 

@@ -14,7 +14,7 @@ from .pipeline import EtaLoop, PtpTables, noise_table
 class BatchEditor:
     def __init__(self, pipe, num_inference_steps=50, eta=((0.6, 0), (1, 0.7)), noise_sample_count=10, seed=0, guidance_scale_bwd=7.5,
                  guidance_scale_fwd=1.0, use_mask=True, mask_thres=0.2, edit_method="ptp"):
-        assert edit_method in ("ptp", "simple", "masactrl")
+        assert edit_method in ("ptp", "simple", "masactrl", "pnp")
         self.pipe, self.S, self.method = pipe, num_inference_steps, edit_method
         self.n_cand, self.seed, self.use_mask = noise_sample_count, seed, use_mask
         pipe.scheduler.set_timesteps(num_inference_steps)
@@ -70,7 +70,11 @@ class BatchEditor:
         unc = self._embed([""])[0]
         c_src, c_tgt = self._embed([s["source_prompt"] for s in sel]), self._embed([s["target_prompt"] for s in sel])
         ctx_src = torch.stack([unc.expand_as(c_src), c_src], 1).contiguous()              # (n,2,77,768)
-        ctx_tgt = torch.stack([unc.expand_as(c_tgt), c_tgt], 1).contiguous()
+        unc_t, pnp = unc, None
+        if self.method == "pnp":            # the target's uncond row is the negative prompt (reference modules/editing/pnp_editor.py:29,58-59)
+            from modules.editing.pnp_editor import NEGATIVE_PROMPT, injection_steps
+            unc_t, pnp = self._embed([NEGATIVE_PROMPT])[0], injection_steps(self.S)
+        ctx_tgt = torch.stack([unc_t.expand_as(c_tgt), c_tgt], 1).contiguous()
         tokens = self._word_tokens([s["source_prompt"] for s in sel]).to(dev) if self.use_mask else None
         inv = self.loop.invert(z0, ctx_src, tokens)
         if self._noise is None:
@@ -78,7 +82,7 @@ class BatchEditor:
         ew = torch.tensor([s["edit_word_idx"][0] for s in sel]) if self.use_mask else None
         ptp = self._ptp_tables(sel) if self.method == "ptp" else None
         masa = (4, 10) if self.method == "masactrl" else None
-        x = self.loop.sample(inv, ctx_src, ctx_tgt, self._noise, edit_word=ew, ptp=ptp, masactrl=masa)   # (2n,4,L,L): [src.., tgt..]
+        x = self.loop.sample(inv, ctx_src, ctx_tgt, self._noise, edit_word=ew, ptp=ptp, masactrl=masa, pnp=pnp)   # (2n,4,L,L): [src.., tgt..]
         images = self.pipe.vae.decode(x / 0.18215)["sample"]
         for k, i in enumerate(ok):
             out[i] = {"image_inv": images[k:k + 1], "image": images[n + k:n + k + 1], "latent_inv": x[k:k + 1], "latent": x[n + k:n + k + 1]}

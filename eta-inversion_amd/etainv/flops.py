@@ -83,3 +83,10 @@ def edict_unet_rows(steps_fwd, steps_bwd, n_img, n_prompts, g_fwd=3.0, g_bwd=3.0
     row of each latent unless the guidance scale is 0 or 1 (one of them)."""
     per_latent = lambda g: 1 if g in (0, 1) else 2
     return 2 * steps_fwd * n_img * per_latent(g_fwd) + 2 * steps_bwd * n_img * n_prompts * per_latent(g_bwd)
+
+
+def pnp_step_rows(step, n_img, conv_steps, qk_steps, source_dead):
+    """UNet sample-forwards of backward step `step` under plug-and-play (etainv.pipeline.EtaLoop.sample, pnp=(conv_steps, qk_steps)): three rows
+    [u_s, u_t, c_t] per image -- the reference's PnPUnetForward cuts the cond source row -- and two, [u_t, c_t], once both injections have ended
+    in a step whose source row is replayed (`source_dead`: eta(t) == 0 under skip_dead_source_rows)."""
+    return (2 if source_dead and step >= max(conv_steps, qk_steps) else 3) * n_img

@@ -18,7 +18,7 @@ import torch
 
 from . import _capi
 from .engine import AttnControl
-from .flops import edict_unet_rows, exit_share
+from .flops import edict_unet_rows, exit_share, pnp_step_rows
 
 NUM_TRAIN = 1000
 
@@ -169,16 +169,27 @@ class EtaLoop:
 
     # ---------------------------------------------------------------- backward / eta sampling
     def sample(self, inv, ctx_src, ctx_tgt, noise, edit_word=None, ptp=None, masactrl=None, trace=None, gt_mask=None, edit_word_tgt=None,
-               teacher=None):
+               teacher=None, pnp=None):
         """noise (S,n_cand,4,L,L) fp32: the candidates of every step (reference draws them from a generator reseeded
         per image, eta_inversion.py:156,276, so all images share the table).  edit_word (B,) index into the word maps.
-        ptp: PtpTables or None; masactrl: (start_step, first_block) or None.  Returns latents (2B,4,L,L) [src.., tgt..].
+        ptp: PtpTables or None; masactrl: (start_step, first_block) or None; pnp: (conv_steps, qk_steps) or None -- plug-and-play, the number of
+        leading backward steps with the feature / the Q,K injection (reference modules/utils/pnp.py:50-54: int(S * 0.8), int(S * 0.5)); ctx_tgt[:, 0] then
+        is the negative-prompt row.  At most one of ptp / masactrl / pnp.  Returns latents (2B,4,L,L) [src.., tgt..].
         teacher (S,2B,4,L,L), tests only: step i starts from teacher[i] (see invert)."""
         e, S, L = self.e, self.S, self.L
         lat_inv = inv["latents"]
         B = lat_inv.shape[1]
         dev = lat_inv.device
+        if sum(c is not None for c in (ptp, masactrl, pnp)) > 1:
+            raise ValueError("ptp, masactrl and pnp are exclusive: one attention coupling per backward pass")
         ctx = torch.cat([ctx_src[:, 0], ctx_tgt[:, 0], ctx_src[:, 1], ctx_tgt[:, 1]]).contiguous().float()   # [u_s,u_t,c_s,c_t] x B
+        ctx_p = eps_p = None
+        if pnp is not None:
+            # PnPUnetForward (pnp.py:130-146): the cond source row is cut, the network runs [u_s, u_t, c_t] and the uncond source noise stands in for the cond
+            # source noise -- the guided source noise u + g (u - u) is u_s itself
+            conv_steps, qk_steps = int(pnp[0]), int(pnp[1])
+            ctx_p = torch.cat([ctx_src[:, 0], ctx_tgt[:, 0], ctx_tgt[:, 1]]).contiguous().float()                # [u_s,u_t,c_t] x B
+            eps_p = torch.empty(3 * B, 4, L, L, dtype=torch.float32, device=dev)
         x = torch.cat([lat_inv[S], lat_inv[S]]).contiguous()
         x_new = torch.empty_like(x)
         eps_all = torch.empty(4 * B, 4, L, L, dtype=torch.float32, device=dev)
@@ -242,6 +253,8 @@ class EtaLoop:
                                        self_replace_active=ptp.self_lo <= i < ptp.self_hi, self_max_tokens=(L // 2) ** 2)
                 elif masactrl is not None:
                     ctrl = AttnControl(mode=_capi.ATTN_MASA, n_img=B, masa_active=masactrl[0] <= i < 50, masa_first_block=masactrl[1])
+                elif pnp is not None:
+                    ctrl = AttnControl(mode=_capi.ATTN_PNP, n_img=B, pnp_qk_active=i < qk_steps, pnp_conv_active=i < conv_steps)
                 if teacher is not None:
                     x.copy_(teacher[i])
                 p = t - self.delta
@@ -271,6 +284,12 @@ class EtaLoop:
                         eu, ec = eps3[:B], eps3[2 * B:]
                         rows_out, layout = eps3, "u_t,c_s,c_t"
                         self.rows_executed += 3 * B
+                    elif pnp is not None and i < max(conv_steps, qk_steps):
+                        # an injection is live: the target rows read the u_s row inside the network, so it runs although nothing reads its noise
+                        e.unet(torch.cat([x[:B], x[B:], x[B:]]), t, ctx_p, ctrl, out=eps_p)
+                        eu, ec = eps_p[B:2 * B], eps_p[2 * B:]
+                        rows_out, layout = eps_p, "u_s,u_t,c_t"
+                        self.rows_executed += pnp_step_rows(i, B, conv_steps, qk_steps, True)
                     else:
                         if ctx3 is None:
                             ctx3 = torch.cat([ctx_tgt[:, 0], ctx_tgt[:, 1]]).contiguous().float()
@@ -292,8 +311,13 @@ class EtaLoop:
                         # the rows this step executed, with their layout (B rows per name); "eps_all" (the 4 B-row layout) does not exist here
                         trace.append({"t": t, "latent": x.clone(), "best": best.clone(), "eps_all": None, "eps_rows": rows_out.clone(), "layout": layout})
                     continue
-                e.unet(x, t, ctx, ctrl, out=eps_all)
-                self.rows_executed += 4 * B
+                if pnp is not None:
+                    e.unet(torch.cat([x[:B], x[B:], x[B:]]), t, ctx_p, ctrl, out=eps_p)
+                    eps_all.view(4, B, 4, L, L).copy_(eps_p.view(3, B, 4, L, L)[[0, 1, 0, 2]])     # rows [0, 1, 0, 2] (pnp.py:146)
+                    self.rows_executed += pnp_step_rows(i, B, conv_steps, qk_steps, False)
+                else:
+                    e.unet(x, t, ctx, ctrl, out=eps_all)
+                    self.rows_executed += 4 * B
                 dmap = None
                 if self.use_mask:
                     raw = src_map(self.mask_eta, i)
@@ -308,8 +332,9 @@ class EtaLoop:
                 if ptp is not None and ptp.blend_alpha is not None and (i + 1) > int(0.2 * S):
                     e.local_blend(x, B, ptp.blend_alpha, 0.3)                       # LocalBlend, reference ptp.py:31-47
                 if trace is not None:
-                    trace.append({"t": t, "latent": x.clone(), "best": best.clone(), "eps_all": eps_all.clone(), "eps_rows": eps_all.clone(),
-                                  "layout": "u_s,u_t,c_s,c_t", "losses": losses.clone()})
+                    trace.append({"t": t, "latent": x.clone(), "best": best.clone(), "eps_all": eps_all.clone(),
+                                  "eps_rows": (eps_all if pnp is None else eps_p).clone(),
+                                  "layout": "u_s,u_t,c_s,c_t" if pnp is None else "u_s,u_t,c_t", "losses": losses.clone()})
         return x
 
 

@@ -26,11 +26,11 @@ from modules import load_diffusion_model  # noqa: E402
 
 
 def parse_args(argv=None):
-    ap = argparse.ArgumentParser(description="PIE-Bench sweep: etainv + {ptp, simple, masactrl} on the MI355X engine")
+    ap = argparse.ArgumentParser(description="PIE-Bench sweep: etainv + {ptp, simple, masactrl, pnp} on the MI355X engine")
     ap.add_argument("--data_path", required=True)
     ap.add_argument("--output", required=True)
     ap.add_argument("--model", default="CompVis/stable-diffusion-v1-4")
-    ap.add_argument("--edit_method", default="ptp", choices=["ptp", "simple", "masactrl"])
+    ap.add_argument("--edit_method", default="ptp", choices=["ptp", "simple", "masactrl", "pnp"])
     ap.add_argument("--batch", type=int, default=32, help="image pairs per engine call and GPU")
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--prec", default="fp16", choices=["fp16", "bf16", "fp32"])

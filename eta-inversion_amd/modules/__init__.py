@@ -1,6 +1,6 @@
 """Registries of the reference's modules/__init__.py:31-111: load_inverter / load_editor / get_inversion_methods /
 get_edit_methods / register_editor.  Built on the MI355X engine: `etainv`, `dirinv`, `edict` (+ the plain `diffinv` base) and the
-`simple`, `ptp`, `masactrl` editors; the reference's other method names are listed but raise a clear error."""
+`simple`, `ptp`, `masactrl`, `pnp` editors; the reference's other method names are listed but raise a clear error."""
 from functools import partial
 from typing import Callable, List
 
@@ -12,18 +12,19 @@ from .editing.editor import Editor
 from .editing.simple_editor import SimpleEditor
 from .editing.ptp_editor import PromptToPromptEditor
 from .editing.masactrl_editor import MasactrlEditor
+from .editing.pnp_editor import PlugAndPlayEditor
 from .models import StablePreprocess, StablePostProc, load_diffusion_model
 
 
 def _not_built(name, *a, **k):
     raise NotImplementedError(f"'{name}' is outside the MI355X hot path built so far (SURVEY.md 8f); available: etainv, dirinv, edict, diffinv / "
-                              f"simple, ptp, masactrl")
+                              f"simple, ptp, masactrl, pnp")
 
 
 _inverters = {"diffinv": DiffusionInversion, "etainv": EtaInversion, "dirinv": DirectInversion, "edict": EdictInversion,
               **{n: partial(_not_built, n) for n in ("nti", "npi", "proxnpi", "ddpminv", "cyclediff", "regdiffinv")}}
-_editors = {"simple": SimpleEditor, "ptp": PromptToPromptEditor, "masactrl": MasactrlEditor,
-            **{n: partial(_not_built, n) for n in ("pnp", "pix2pix_zero", "invedit")}}
+_editors = {"simple": SimpleEditor, "ptp": PromptToPromptEditor, "masactrl": MasactrlEditor, "pnp": PlugAndPlayEditor,
+            **{n: partial(_not_built, n) for n in ("pix2pix_zero", "invedit")}}
 
 
 def register_editor(name: str, editor_cls: Callable) -> None:

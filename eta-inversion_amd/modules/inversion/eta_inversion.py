@@ -122,22 +122,25 @@ class EtaInversion(DiffusionInversion):
 
     # ------------------------------------------------------------------ backward
     def _tables_from_controller(self):
-        """(PtpTables | None, masactrl | None, fast_path_ok)"""
+        """(PtpTables | None, masactrl | None, pnp | None, fast_path_ok)"""
         from ..editing.ptp_editor import PromptToPromptController
         from ..editing.masactrl_editor import MasactrlController
+        from ..editing.pnp_editor import PnpController
         c = self.controller
         if isinstance(c, ControllerEmpty):
-            return None, None, True
+            return None, None, None, True
+        if isinstance(c, PnpController):
+            return None, None, (c.conv_steps, c.qk_steps), True
         if isinstance(c, PromptToPromptController):
             t = c.controller.tables()
             st = lambda a: None if a is None else a[None]
             ptp = PtpTables(st(t["mapper"]), st(t["alphas"]), t["cross_alpha"][:, None], c.controller.self_replace_steps,
                             self.num_inference_steps, equalizer=st(t["equalizer"]), blend_alpha=st(t["blend_alpha"]),
                             replace_mat=st(t["replace_mat"]), device=self.model.device)
-            return ptp, None, True
+            return ptp, None, None, True
         if isinstance(c, MasactrlController):
-            return None, (c.step, c.layer), True
-        return None, None, False
+            return None, (c.step, c.layer), None, True
+        return None, None, None, False
 
     def diffusion_backward(self, latent, context, inv_result):
         if latent.shape[0] != 2:
@@ -146,7 +149,7 @@ class EtaInversion(DiffusionInversion):
         S, L = self.num_inference_steps, self.L
         inv_cfg = inv_result.get("inv_cfg") or {}
         edit_word_idx = inv_cfg.get("edit_word_idx", None)
-        ptp, masa, fast = self._tables_from_controller()
+        ptp, masa, pnp, fast = self._tables_from_controller()
         generator = torch.Generator().manual_seed(self.seed) if self.seed is not None else None
         # force_per_step (attribute, default off): run the reference-style callback-per-step path also for the built-in controllers
         if fast and latent.shape[0] == 2 and "_native" in inv_result and not getattr(self, "force_per_step", False):
@@ -161,7 +164,7 @@ class EtaInversion(DiffusionInversion):
                 gt = torch.nn.functional.interpolate(gt.float().reshape(1, 1, *gt.shape[-2:]), (L, L), mode="bilinear")[0]
             ew_t = torch.tensor([edit_word_idx[1]]) if self.mask_mode_cfg is not None else None
             return self._loop.sample(inv_result["_native"], ctx_src, ctx_tgt, noise, edit_word=ew, ptp=ptp, masactrl=masa, gt_mask=gt,
-                                     edit_word_tgt=ew_t)
+                                     edit_word_tgt=ew_t, pnp=pnp)
         # generic path: user-defined controllers keep their per-step callbacks
         mask = inv_cfg.get("mask", None)
         if mask is not None:                                               # eta_inversion.py:286-287

@@ -10,6 +10,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
+from etainv import _capi
 from etainv.engine import Engine
 from etainv.nets import NativeCLIPText, NativeVAE
 from etainv.weights import load_component
@@ -28,6 +29,13 @@ class NativeUNet:
     def __call__(self, sample, timestep, encoder_hidden_states=None):
         n = encoder_hidden_states.shape[0]
         assert sample.shape[0] == n, "latent and context batch must match (duplicate the latent for CFG)"
+        if self.attn_ctrl is not None and self.attn_ctrl.c.mode == _capi.ATTN_PNP:
+            # PnPUnetForward (reference modules/utils/pnp.py:130-146): of [u_s, u_t, c_s, c_t] the cond source row is cut, the network runs
+            # [u_s, u_t, c_t] and the uncond source noise is returned in the cond source row's place
+            if n != 4:
+                raise ValueError(f"plug-and-play runs one [source, target] pair per UNet call: 4 rows [u_s, u_t, c_s, c_t], got {n}")
+            eps = self.engine.unet(sample[[0, 1, 3]].to(self.dtype), timestep, encoder_hidden_states[[0, 1, 3]].to(self.dtype), self.attn_ctrl)
+            return {"sample": eps[[0, 1, 0, 2]]}
         eps = self.engine.unet(sample.to(self.dtype), timestep, encoder_hidden_states.to(self.dtype), self.attn_ctrl)
         return {"sample": eps}
 

@@ -135,7 +135,7 @@ int etainv_engine_weights_ready(etainv_engine_t* e); /* 1 when every parameter h
 /* Declarative attention control for one UNet call: replaces the per-layer Python callbacks installed by
  * register_attention_control (modules/utils/ptp_utils.py:196-302) and register_attention_editor_diffusers
  * (modules/utils/masactrl_utils.py:74-153).  Device pointers; per-image tables have n_img rows. */
-enum etainv_attn_mode { ETAINV_ATTN_PLAIN = 0, ETAINV_ATTN_STORE = 1, ETAINV_ATTN_PTP = 2, ETAINV_ATTN_MASA = 3 };
+enum etainv_attn_mode { ETAINV_ATTN_PLAIN = 0, ETAINV_ATTN_STORE = 1, ETAINV_ATTN_PTP = 2, ETAINV_ATTN_MASA = 3, ETAINV_ATTN_PNP = 4 };
 
 typedef struct etainv_attn_ctrl {
   int mode;
@@ -169,7 +169,14 @@ typedef struct etainv_attn_ctrl {
    * must lie behind the last (L/2)^2-token self-attention (block 12); with store_maps it must not lie in front of the last layer the store keeps
    * (etainv_maps_configure: res_div 2 -> block 12, 4 -> block 9, 8 -> block 6) -- an earlier exit is an error, not a silent loss of maps. */
   int src_exit_block;
-  int reserved[2];
+  /* PNP (plug-and-play; register_attention_control_efficient / register_conv_control_efficient, modules/utils/pnp_utils.py, under PnPUnetForward,
+   * modules/utils/pnp.py): the call carries n_rows == 3 n_img rows [u_s, u_t, c_t] x n_img over n_lat == n_rows latents [src, tgt, tgt] x n_img -- the
+   * reference cuts the cond source row and returns the uncond source noise in its place.  No store, no tables, first_row == src_exit_block == 0.
+   * pnp_qk_active: in the self-attention of transformer blocks 8..15 (execution order; up_blocks[1].attentions[1, 2], up_blocks[2, 3].attentions[0..2]) the
+   * target rows take Q and K of the u_s row of their image, V stays their own.  pnp_conv_active: in up_blocks[1].resnets[1] the conv2 output (bias
+   * included, before the shortcut add) of the target rows is that of the u_s row of their image.  Both 0: the plain call. */
+  int pnp_qk_active;
+  int pnp_conv_active;
 } etainv_attn_ctrl;
 
 /* eps = UNet(latent, t, ctx).  Replaces `self.unet(latent_input, t, encoder_hidden_states=context)["sample"]`
@@ -317,11 +324,13 @@ int etainv_op_groupnorm(const void* x_nhwc, const void* x2_nhwc, int c1, int c2,
                         float* scratch, int dtype, void* stream);
 int etainv_op_layernorm(const void* x, const float* gamma, const float* beta, void* out, int rows, int c,
                         float eps, int dtype, void* stream);
-/* mode 0 plain, 1 ptp self-replace, 2 masactrl (modes 1/2: b == 4*n_img rows [u_s,u_t,c_s,c_t]) */
+/* mode 0 plain, 1 ptp self-replace, 2 masactrl (modes 1/2: b == 4*n_img rows [u_s,u_t,c_s,c_t]), 3 plug-and-play (b == 3*n_img rows [u_s,u_t,c_t]:
+ * rows >= n_img take Q and K of row r % n_img, V stays their own).  A row count that does not fit the mode's layout is an error; nothing is launched. */
 int etainv_op_self_attention(const void* qkv, void* out, int b, int n, int heads, int d, int mode, int n_img,
                              int dtype, void* stream);
 /* The same launch with every argument the UNet passes.  q_prescaled: the queries already carry head_dim^-0.5 * log2(e) (head_dim 40 / 80, 16-bit types);
- * first_row: 0 = all 4 n_img rows, n_img = rows [u_t, c_s, c_t] (mode 1), < 0 = rows [u_t, c_t, c_s] (mode 1, b == 3 n_img; see etainv_attn_ctrl);
+ * first_row: 0 = all 4 n_img rows (mode 3: all 3 n_img rows, the only value it takes), n_img = rows [u_t, c_s, c_t] (mode 1), < 0 = rows [u_t, c_t, c_s]
+ * (mode 1, b == 3 n_img; see etainv_attn_ctrl);
  * head_major: qkv holds three planes [q|k|v][b][heads][n][d] instead of rows [b][n][3 heads d] (head_dim 40 / 80, 16-bit types; else an error). */
 int etainv_op_self_attention_ex(const void* qkv, void* out, int b, int n, int heads, int d, int mode, int n_img,
                                 int q_prescaled, int first_row, int head_major, int dtype, void* stream);
@@ -360,6 +369,9 @@ int etainv_op_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int
 int etainv_op_im2col_in(const void* latent, int io_dtype, int n_lat, int rows, int l, void* out, int dtype, void* stream);
 int etainv_op_pack_weight(const float* src, void* dst, int64_t rows, int64_t cols, int mode, int taps, float scale, const float* colscale,
                           int dtype, void* stream);
+/* Plug-and-play feature injection as resblock() launches it: of the activation x [rows][row_elems] (in place) every row r >= n_src becomes a copy of row
+ * r % n_src; rows < n_src are only read.  Refused: null x, rows % n_src != 0, a row whose byte size is not a multiple of 16. */
+int etainv_op_rows_broadcast(void* x, int rows, int n_src, int64_t row_elems, int dtype, void* stream);
 /* etainv_op_gemm with an fp32 result [m][n]: the one GEMM of all time-embedding projections (ResnetBlock2D.time_emb_proj, n = 20160) */
 int etainv_op_gemm_f32out(const void* a, const void* w, const float* bias, float* out_f32, int m, int n, int k, int dtype, void* stream);
 /* etainv_op_conv3x3 whose time row is read as the UNet reads it: row i of rowvec starts at rowvec + i * rowvec_stride (a column block of that matrix) */
