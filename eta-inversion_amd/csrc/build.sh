@@ -3,7 +3,7 @@
 set -e
 HERE="$(cd "$(dirname "$0")" && pwd)"
 OUT="$HERE/../etainv/lib"
-OBJ="$HERE/obj"; LIBNAME=libetainv_hip.so; SRCS="step_kernels igemm norm attention misc maps aux_nets f32path ppgemm ppconv"
+OBJ="$HERE/obj"; LIBNAME=libetainv_hip.so; SRCS="step_kernels regularize igemm norm attention misc maps aux_nets f32path ppgemm ppconv"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result"
 mkdir -p "$OUT" "$OBJ"
 pids=()
@@ -23,6 +23,13 @@ for p in "${pids[@]}"; do wait $p; done
 objs=""; for f in $SRCS engine; do objs="$objs $OBJ/$f.o"; done
 hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/$LIBNAME" $objs
 echo "built $OUT/$LIBNAME"
+# regularize.hip steers its register allocation (opaque copies of the thread index, scheduling fences every four slots: DESIGN 4.9b), which a
+# compiler change can undo without any test failing.  Expected with these flags, noise_regularize_kernel<MAXQ, L0_LDS> at 1024 threads (128
+# VGPRs available): <4, true> 48 VGPRs, <16, true> 120 VGPRs, <36, false> 128 VGPRs + 276 spilled dwords (580 B scratch); no spill in the first
+# two.  RESOURCES=1 prints what this compiler gives (the lines to compare are "VGPRs:", "VGPRs Spill:", "ScratchSize").
+if [ "${RESOURCES:-0}" = "1" ]; then
+  hipcc $FLAGS --cuda-device-only -Rpass-analysis=kernel-resource-usage -c "$HERE/regularize.hip" -o /dev/null 2>&1 | grep -E "Function Name|VGPRs|ScratchSize" || true
+fi
 # diagnostic variant (STAMPS=1): igemm with in-kernel s_memtime stamps -> lib/libetainv_hip_stamps.so (load it with ETAINV_LIB=<path>;
 # tools/experiments/*: reads SHARES of a K step, never a run time)
 if [ "${STAMPS:-0}" = "1" ]; then

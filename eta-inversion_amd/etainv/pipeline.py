@@ -70,8 +70,11 @@ class EtaLoop:
 
     def __init__(self, engine, S=50, guidance_scale_bwd=7.5, guidance_scale_fwd=1.0, eta=(0.0, 0.4), noise_sample_count=10,
                  use_mask=True, mask_thres=0.2, skip_uncond_fwd=True, steps_offset=0, mask_eta="fwd_mean", mask_pow=None, target_dirinv=None,
-                 mask_dirinv=None, skip_dead_source_rows=True, attn_res=None, attn_from_where=("up", "down")):
+                 mask_dirinv=None, skip_dead_source_rows=True, attn_res=None, attn_from_where=("up", "down"), regularizer=None):
         self.e, self.S, self.L = engine, S, engine.L
+        # NoiseRegularizer or None: `invert` then pushes every guided noise towards white noise before the DDIM step (regularised DDIM inversion,
+        # reference modules/inversion/regularized_diffusion_inversion.py:116-137), CFG combine, regularisation and step in one launch
+        self.regularizer = regularizer
         # which cross layers the eta mask's word maps average (mask_mode_cfg attn_res / attn_from_where, eta_inversion.py:161-162; aggregate_attention
         # ptp.py:288-303: the layers with res^2 tokens of the named locations, `res == 8` -> the mid block whatever from_where says)
         self.attn_div, self.attn_layer_mask = attn_layer_selection(self.L, attn_res, attn_from_where)
@@ -95,6 +98,8 @@ class EtaLoop:
         assert target_dirinv is None or use_mask, "target_dirinv is part of the masked update"
         # u + 1*(c - u) == c up to rounding: the uncond half of the forward pass is dead work when g_fwd == 1
         self.skip_uncond_fwd = skip_uncond_fwd and self.g_fwd == 1.0 and self.g_fwd_table is None
+        if regularizer is not None and regularizer.L != self.L:
+            raise ValueError(f"the regulariser was built for {regularizer.L} x {regularizer.L} latents, the engine runs {self.L} x {self.L}")
         # Backward steps with eta(t) == 0 (the whole ramp-free part of the paper's schedule: 30 of 50 steps with eta [[0.6, 0], [1, 0.7]]): the source
         # row is REPLAYED from the inversion trajectory (eta_inversion.py:247-249) and its guided noise feeds nothing but the best-of-n choice of a
         # noise sample that is then multiplied by eta sigma = 0 (:232, :330-375) -- eps(uncond source) is dead work.  Those steps run 3 B UNet rows
@@ -121,7 +126,8 @@ class EtaLoop:
     # ---------------------------------------------------------------- forward / inversion
     def invert(self, z0, ctx_src, tokens=None, teacher=None):
         """z0 (B,4,L,L) fp32; ctx_src (B,2,77,768) = [uncond, cond] per image; tokens (B,W) int32 token index of each
-        whitespace word (first occurrence + 1).  Returns latents (S+1,B,4,L,L) and the mean word maps (B,W,L,L).
+        whitespace word (first occurrence + 1).  Returns latents (S+1,B,4,L,L) and the mean word maps (B,W,L,L); with a regulariser also
+        "noise_preds" (S,B,4,L,L), the regularised noise of every step.
         teacher (S+1,B,4,L,L), tests only: step j reads teacher[j] instead of its own previous output (teacher-forced parity:
         every step is compared with the oracle on the oracle's input, so rounding is not amplified by the recursion)."""
         e, S, L = self.e, self.S, self.L
@@ -136,6 +142,8 @@ class EtaLoop:
         rows = ctx.shape[0]
         eps_all = torch.empty(rows, 4, L, L, dtype=torch.float32, device=dev)
         eps = eps_all if self.skip_uncond_fwd else torch.empty(B, 4, L, L, dtype=torch.float32, device=dev)
+        reg = self.regularizer
+        eps_reg = torch.empty(S, B, 4, L, L, dtype=torch.float32, device=dev) if reg is not None else None
         maps_mean = maps_steps = None
         ctrl = None
         if self.use_mask:
@@ -155,17 +163,27 @@ class EtaLoop:
                 x_in = lat[j] if teacher is None else teacher[j].contiguous()
                 e.unet(x_in, int(t), ctx, ctrl, out=eps_all)
                 self.rows_executed += rows
-                if not self.skip_uncond_fwd:
-                    g = float(self.g_fwd_table[int(t)]) if self.g_fwd_table is not None else self.g_fwd
-                    _capi.check(self.lib.etainv_cfg_combine(_capi.ptr(eps_all[:B]), _capi.ptr(eps_all[B:]), g, _capi.ptr(eps), n,
-                                                            _capi.F32, st))
                 a_from, a_to = self._alpha(int(t) - self.delta), self._alpha(int(t))   # "sameshift" (scheduling_ddim_inverse.py:127-131)
-                _capi.check(self.lib.etainv_ddim_step(_capi.ptr(x_in), _capi.ptr(eps), a_from, a_to, _capi.ptr(lat[j + 1]), n, _capi.F32, st))
+                if reg is not None:
+                    if self.skip_uncond_fwd:                   # one row per image: the noise already is the guided one
+                        reg.run(self.lib, None, eps_all, 1.0, eps_reg[j], x_in, a_from, a_to, lat[j + 1], B, st)
+                    else:
+                        g = float(self.g_fwd_table[int(t)]) if self.g_fwd_table is not None else self.g_fwd
+                        reg.run(self.lib, eps_all[:B], eps_all[B:], g, eps_reg[j], x_in, a_from, a_to, lat[j + 1], B, st)
+                else:
+                    if not self.skip_uncond_fwd:
+                        g = float(self.g_fwd_table[int(t)]) if self.g_fwd_table is not None else self.g_fwd
+                        _capi.check(self.lib.etainv_cfg_combine(_capi.ptr(eps_all[:B]), _capi.ptr(eps_all[B:]), g, _capi.ptr(eps), n,
+                                                                _capi.F32, st))
+                    _capi.check(self.lib.etainv_ddim_step(_capi.ptr(x_in), _capi.ptr(eps), a_from, a_to, _capi.ptr(lat[j + 1]), n, _capi.F32, st))
                 if self.use_mask:
                     e.word_maps_ex(B, tokens, j + 1, 0, self.attn_layer_mask, maps_mean, accumulate=True, scale=1.0 / S)
                     if maps_steps is not None:
                         e.word_maps_ex(B, tokens, j + 1, 0, self.attn_layer_mask, maps_steps[j], accumulate=False, scale=1.0)
-        return {"latents": lat, "maps_mean": maps_mean, "maps_steps": maps_steps}
+        res = {"latents": lat, "maps_mean": maps_mean, "maps_steps": maps_steps}
+        if reg is not None:
+            res["noise_preds"] = eps_reg
+        return res
 
     # ---------------------------------------------------------------- backward / eta sampling
     def sample(self, inv, ctx_src, ctx_tgt, noise, edit_word=None, ptp=None, masactrl=None, trace=None, gt_mask=None, edit_word_tgt=None,
@@ -364,6 +382,58 @@ def noise_table(S, n, L, seed=0, device="cuda"):
     """CPU torch generator, reseeded per image like the reference (eta_inversion.py:276): one table for all images."""
     g = torch.Generator().manual_seed(seed)
     return torch.stack([torch.randn((n, 1, 4, L, L), generator=g) for _ in range(S)]).reshape(S, n, 4, L, L).to(device)
+
+
+# ---------------------------------------------------------------- regularised DDIM inversion (reference modules/inversion/regularized_diffusion_inversion.py)
+def regdiff_level_sizes(L):
+    """sides of auto_corr_loss's average-pool pyramid (:61-68): the loss at a level, then pool while the level is above 8"""
+    sizes = [int(L)]
+    while sizes[-1] > 8:
+        sizes.append(sizes[-1] // 2)
+    return sizes
+
+
+def regdiff_shift_table(L, num_reg_steps=5, num_ac_rolls=5, lambda_ac=20.0, generator=None, seed=0):
+    """int32 [num_reg_steps * num_ac_rolls][4][levels]: the roll amounts of regularize_noise_pred (:86-114) in the order the reference draws
+    them -- autocorrelation step, channel, level from fine to coarse, each one `torch.randint(0, s // 2, ())` (:62).  generator None: a fresh
+    CPU generator with `seed`; the reference reseeds to 0 at every inversion step (:117), so one table serves all steps.  Nothing is drawn
+    with lambda_ac <= 0 (:99)."""
+    sizes = regdiff_level_sizes(L)
+    n = int(num_reg_steps) * int(num_ac_rolls) if lambda_ac > 0 else 0
+    g = generator if generator is not None else torch.Generator().manual_seed(seed)
+    table = np.zeros((n, 4, len(sizes)), dtype=np.int32)
+    for a in range(n):
+        for c in range(4):
+            for k, s in enumerate(sizes):
+                table[a, c, k] = torch.randint(0, s // 2, (), generator=g).item()
+    return table
+
+
+class NoiseRegularizer:
+    """The four parameters of the noise regularisation and the device shift table (built once), and the call of etainv_noise_regularize."""
+
+    def __init__(self, L, lambda_ac=20.0, lambda_kl=20.0, num_reg_steps=5, num_ac_rolls=5, device="cuda", seed=0):
+        self.L, self.lambda_ac, self.lambda_kl = int(L), float(lambda_ac), float(lambda_kl)
+        self.num_reg_steps, self.num_ac_rolls = int(num_reg_steps), int(num_ac_rolls)
+        self.device, self.seed = device, seed
+        self._shifts, self._built = None, False
+
+    def table(self, generator=None):
+        """device table of the draws of `generator`, or (built once) of a fresh generator with the regulariser's seed; None when nothing is drawn"""
+        if generator is None and self._built:
+            return self._shifts
+        host = regdiff_shift_table(self.L, self.num_reg_steps, self.num_ac_rolls, self.lambda_ac, generator, self.seed)
+        dev = torch.from_numpy(host).to(self.device).contiguous() if host.size else None
+        if generator is None:
+            self._shifts, self._built = dev, True
+        return dev
+
+    def run(self, lib, eps_u, eps_c, g, eps_out, x, a_from, a_to, x_out, n_img, stream, shifts=None):
+        """eps_u / x None: no CFG combine / no DDIM step (see include/etainv.h)"""
+        shifts = shifts if shifts is not None else self.table()
+        _capi.check(lib.etainv_noise_regularize(_capi.ptr(eps_u), _capi.ptr(eps_c), float(g), _capi.ptr(eps_out), _capi.ptr(x), float(a_from), float(a_to),
+                                                _capi.ptr(x_out), int(n_img), self.L, _capi.ptr(shifts), self.num_reg_steps, self.num_ac_rolls,
+                                                self.lambda_ac, self.lambda_kl, stream))
 
 
 # ---------------------------------------------------------------- EDICT host tables (reference modules/inversion/edict_inversion.py)

@@ -1,5 +1,5 @@
 """Registries of the reference's modules/__init__.py:31-111: load_inverter / load_editor / get_inversion_methods /
-get_edit_methods / register_editor.  Built on the MI355X engine: `etainv`, `dirinv`, `edict` (+ the plain `diffinv` base) and the
+get_edit_methods / register_editor.  Built on the MI355X engine: `etainv`, `dirinv`, `edict`, `regdiffinv` (+ the plain `diffinv` base) and the
 `simple`, `ptp`, `masactrl`, `pnp` editors; the reference's other method names are listed but raise a clear error."""
 from functools import partial
 from typing import Callable, List
@@ -8,6 +8,7 @@ from .inversion.diffusion_inversion import DiffusionInversion
 from .inversion.eta_inversion import EtaInversion
 from .inversion.direct_inversion import DirectInversion
 from .inversion.edict_inversion import EdictInversion
+from .inversion.regularized_diffusion_inversion import RegularizedDiffusionInversion
 from .editing.editor import Editor
 from .editing.simple_editor import SimpleEditor
 from .editing.ptp_editor import PromptToPromptEditor
@@ -17,12 +18,13 @@ from .models import StablePreprocess, StablePostProc, load_diffusion_model
 
 
 def _not_built(name, *a, **k):
-    raise NotImplementedError(f"'{name}' is outside the MI355X hot path built so far (SURVEY.md 8f); available: etainv, dirinv, edict, diffinv / "
+    raise NotImplementedError(f"'{name}' is outside the MI355X hot path built so far (SURVEY.md 8f); available: etainv, dirinv, edict, regdiffinv, diffinv / "
                               f"simple, ptp, masactrl, pnp")
 
 
 _inverters = {"diffinv": DiffusionInversion, "etainv": EtaInversion, "dirinv": DirectInversion, "edict": EdictInversion,
-              **{n: partial(_not_built, n) for n in ("nti", "npi", "proxnpi", "ddpminv", "cyclediff", "regdiffinv")}}
+              "regdiffinv": RegularizedDiffusionInversion,
+              **{n: partial(_not_built, n) for n in ("nti", "npi", "proxnpi", "ddpminv", "cyclediff")}}
 _editors = {"simple": SimpleEditor, "ptp": PromptToPromptEditor, "masactrl": MasactrlEditor, "pnp": PlugAndPlayEditor,
             **{n: partial(_not_built, n) for n in ("pix2pix_zero", "invedit")}}
 

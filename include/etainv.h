@@ -105,6 +105,20 @@ int etainv_edict_mix(void* x, void* y, float p, int inverse, int64_t n, int io_d
 int etainv_edict_couple_mix(void* x, void* y, int base_is_y, const void* eps_u, const void* eps_c, float g, float a, float b, float p,
                             int64_t n, int io_dtype, void* stream);
 
+/* ---- regularised DDIM inversion (pix2pix-zero; reference modules/inversion/regularized_diffusion_inversion.py)
+ * Everything of RegularizedDiffusionInversion.predict_step_forward (:116-137) after the UNet call, one launch, for n_img images of
+ * [4][l][l] fp32: the CFG combine (eps_u NULL: eps_c already is the guided noise and g is ignored), regularize_noise_pred (:86-114:
+ * num_reg_steps rounds of num_ac_rolls gradient steps on auto_corr_loss :42-69, each weighted lambda_ac / num_ac_rolls, and one gradient
+ * step on kl_divergence :71-83 weighted lambda_kl -- both gradients in closed form, no autograd), and the DDIM inverse step of
+ * etainv_ddim_step on the regularised noise (x NULL: no step; a_from / a_to as there).  eps_out receives the regularised noise and may be
+ * eps_c.  shifts_dev, device int32 [num_reg_steps * num_ac_rolls][4][levels]: the roll amount of every autocorrelation step, channel and
+ * pyramid level (fine to coarse; the levels are l, l/2, .. while a level is above 8), the reference's torch.randint(0, s // 2) draws in its
+ * order; needed only when lambda_ac > 0 and both counts are positive.  8 <= l <= 96.  num_reg_steps == 0 or both lambdas <= 0: the noise
+ * passes unchanged.  An image's result does not depend on n_img or on its position and is bit-identical from run to run. */
+int etainv_noise_regularize(const float* eps_u, const float* eps_c, float g, float* eps_out, const float* x, float a_from, float a_to,
+                            float* x_out, int n_img, int l, const int32_t* shifts_dev, int num_reg_steps, int num_ac_rolls,
+                            float lambda_ac, float lambda_kl, void* stream);
+
 /* ---------------------------------------------------------------- engine */
 typedef struct etainv_engine etainv_engine_t;
 
