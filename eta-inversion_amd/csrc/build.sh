@@ -3,7 +3,7 @@
 set -e
 HERE="$(cd "$(dirname "$0")" && pwd)"
 OUT="$HERE/../etainv/lib"
-OBJ="$HERE/obj"; LIBNAME=libetainv_hip.so; SRCS="step_kernels regularize igemm norm attention misc maps aux_nets f32path ppgemm ppconv"
+OBJ="$HERE/obj"; LIBNAME=libetainv_hip.so; SRCS="step_kernels regularize proximal igemm norm attention misc maps aux_nets f32path ppgemm ppconv"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result"
 mkdir -p "$OUT" "$OBJ"
 pids=()
@@ -27,8 +27,12 @@ echo "built $OUT/$LIBNAME"
 # compiler change can undo without any test failing.  Expected with these flags, noise_regularize_kernel<MAXQ, L0_LDS> at 1024 threads (128
 # VGPRs available): <4, true> 48 VGPRs, <16, true> 120 VGPRs, <36, false> 128 VGPRs + 276 spilled dwords (580 B scratch); no spill in the first
 # two.  RESOURCES=1 prints what this compiler gives (the lines to compare are "VGPRs:", "VGPRs Spill:", "ScratchSize").
+# proximal.hip keeps up to 32 values per thread in registers through five passes.  Expected, prox_guidance_kernel<Q> at 1024 threads:
+# <4> 46 VGPRs, <32> 110 VGPRs, <0> 42 VGPRs; no spill and no scratch in any of the three; 17,424 B of LDS each.
 if [ "${RESOURCES:-0}" = "1" ]; then
-  hipcc $FLAGS --cuda-device-only -Rpass-analysis=kernel-resource-usage -c "$HERE/regularize.hip" -o /dev/null 2>&1 | grep -E "Function Name|VGPRs|ScratchSize" || true
+  for f in regularize proximal; do
+    hipcc $FLAGS --cuda-device-only -Rpass-analysis=kernel-resource-usage -c "$HERE/$f.hip" -o /dev/null 2>&1 | grep -E "Function Name|VGPRs|ScratchSize" || true
+  done
 fi
 # diagnostic variant (STAMPS=1): igemm with in-kernel s_memtime stamps -> lib/libetainv_hip_stamps.so (load it with ETAINV_LIB=<path>;
 # tools/experiments/*: reads SHARES of a K step, never a run time)

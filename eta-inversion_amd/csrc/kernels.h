@@ -182,6 +182,12 @@ int launch_cast_f32(const void* src, int src_dtype, void* dst, int dst_dtype, in
 // a whole number of 16-byte vectors
 int launch_rows_broadcast(void* x, int rows, int n_src, int64_t row_elems, int dtype, hipStream_t s);
 
+// ---- proximal.hip
+// etainv_prox_guidance (include/etainv.h) behind its stream cast: every refusal is made here, before anything touches the device
+int launch_prox_guidance(const float* eps_u, const float* eps_c, float g, int mode, int use_rank, int rank_lo, float rank_w, float thr_fixed,
+                         float* eps_out, const float* x, float a_from, float a_to, float* x_out, float* thr_out, int n_groups, int rows_per_group,
+                         int l, hipStream_t s);
+
 // ---- maps.hip
 int launch_word_maps(const float* maps_acc, int n_layers, int n_img_cap, int rows_per_img, int row_sel, int heads, int res, int L,
                      int n_img, const int32_t* tokens, int n_tok, int steps_done, float* out, int accumulate, float scale,

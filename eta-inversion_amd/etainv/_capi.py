@@ -43,6 +43,7 @@ SIGNATURES = {
     "etainv_edict_mix": [_p, _p, _f, _i, _i64, _i, _p],
     "etainv_edict_couple_mix": [_p, _p, _i, _p, _p, _f, _f, _f, _f, _i64, _i, _p],
     "etainv_noise_regularize": [_p, _p, _f, _p, _p, _f, _f, _p, _i, _i, _p, _i, _i, _f, _f, _p],
+    "etainv_prox_guidance": [_p, _p, _f, _i, _i, _i, _f, _f, _p, _p, _f, _f, _p, _p, _i, _i, _i, _p],
     "etainv_engine_create": [C.POINTER(EngineConfig), C.POINTER(_p)],
     "etainv_engine_destroy": [_p],
     "etainv_engine_num_weights": [_p],

@@ -436,6 +436,42 @@ class NoiseRegularizer:
                                                 self.lambda_ac, self.lambda_kl, stream))
 
 
+# ---------------------------------------------------------------- proximal guidance (reference modules/inversion/proximal_negative_prompt_inversion.py)
+class ProximalGuidance:
+    """The parameters of proximal_guidance (:61-128), the rank split of its torch.quantile, and the call of etainv_prox_guidance.
+    prox None: plain CFG; "l0" / "l1": the two shrinkages; anything else is refused at the call, as the reference does.  quantile > 0: the
+    threshold is that quantile of |eps_c - eps_u| over a group; quantile <= 0: the fixed threshold -quantile."""
+    MODES = {None: 0, "l0": 1, "l1": 2}
+
+    def __init__(self, L, prox="l0", quantile=0.7):
+        if quantile > 1:
+            raise ValueError(f"quantile must be at most 1 (a quantile of |eps_c - eps_u|) or <= 0 (a fixed threshold), got {quantile}")
+        self.L, self.prox, self.quantile = int(L), prox, float(quantile)
+
+    @staticmethod
+    def rank_split(n, q):
+        """(k, w) of torch.quantile(x, q) over n fp32 values, linear interpolation: rank = float32(q) * (n - 1) in fp32, k = floor(rank),
+        w = rank - k; the quantile is lerp(sorted[k], sorted[min(k + 1, n - 1)], w)"""
+        rank = np.float32(q) * np.float32(n - 1)
+        k = min(int(np.floor(rank)), n - 1)
+        return k, float(np.float32(rank - np.float32(k)))
+
+    def run(self, lib, eps_u, eps_c, g, eps_out, x, a_from, a_to, x_out, n_groups, rows_per_group, stream=None, thr_out=None):
+        """x None: no DDIM step; stream None: torch's current stream (see include/etainv.h)"""
+        if self.prox not in self.MODES:
+            raise NotImplementedError(f"proximal guidance '{self.prox}' is not defined (None, 'l0', 'l1')")
+        mode = self.MODES[self.prox]
+        use_rank, k, w, thr = 0, 0, 0.0, 0.0
+        if mode and self.quantile > 0:
+            use_rank = 1
+            k, w = self.rank_split(int(rows_per_group) * 4 * self.L * self.L, self.quantile)
+        elif mode:
+            thr = 0.0 - self.quantile
+        _capi.check(lib.etainv_prox_guidance(_capi.ptr(eps_u), _capi.ptr(eps_c), float(g), mode, use_rank, k, w, thr, _capi.ptr(eps_out), _capi.ptr(x),
+                                             float(a_from), float(a_to), _capi.ptr(x_out), _capi.ptr(thr_out), int(n_groups), int(rows_per_group),
+                                             self.L, stream if stream is not None else _capi.stream_ptr()))
+
+
 # ---------------------------------------------------------------- EDICT host tables (reference modules/inversion/edict_inversion.py)
 def edict_timesteps(S, init_image_strength=1.0):
     """(forward, backward) timesteps that run: the scheduler's leading-spaced S timesteps with the t_limit = S - int(S strength) noisiest

@@ -119,6 +119,24 @@ int etainv_noise_regularize(const float* eps_u, const float* eps_c, float g, flo
                             float* x_out, int n_img, int l, const int32_t* shifts_dev, int num_reg_steps, int num_ac_rolls,
                             float lambda_ac, float lambda_kl, void* stream);
 
+/* ---- proximal negative-prompt inversion (reference modules/inversion/proximal_negative_prompt_inversion.py)
+ * Everything of ProximalNegativePromptInversion.predict_noise (:130-151) after the UNet call, one launch, all tensors fp32:
+ * d = eps_c - eps_u, the threshold, the shrinkage of proximal_guidance (:61-128), eps_out = eps_u + g d', and optionally the DDIM step of
+ * etainv_ddim_step on eps_out (x NULL: no step; a_from / a_to as there; x and x_out have the rows of the noise).
+ * Rows: n_groups groups of rows_per_group rows of [4][l][l]; row r of group j is tensor row r * n_groups + j (the [src.., tgt..] order of
+ * etainv_eta_backward_step).  The n = rows_per_group * 4 * l * l values of a group share one threshold.  1 <= rows_per_group <= 4, 8 <= l <= 96.
+ * mode 0: plain CFG (no threshold; bit-equal to mode 1 with a fixed threshold of 0); 1: "l0", d' = d - clamp(d, -thr, thr); 2: "l1", then
+ * d' = d' > 0 ? d' - thr : d', then d' = d' < 0 ? d' + thr : d', in that order (:88-90, not symmetric).
+ * Threshold, modes 1 and 2: use_rank != 0: torch.quantile of |d| over the group at the rank the host split into rank_lo = k in [0, n - 1]
+ * and rank_w = w in [0, 1): thr = lerp(v_k, v_min(k+1, n-1), w) by torch's rule (v_k + w diff below w = 0.5, v_k+1 - diff (1 - w) from there),
+ * v the exact order statistics (a radix select over the bit patterns; -0.0 counts as 0, +inf sorts last, a NaN anywhere in a group makes its
+ * threshold and its noise NaN).  use_rank == 0: thr = thr_fixed >= 0.
+ * eps_out may be eps_c (not eps_u).  thr_out (may be NULL): [n_groups][3] = (thr, v_k, v_k+1); with a fixed threshold all three are thr.
+ * A group's result does not depend on n_groups or on its position and is bit-identical from run to run. */
+int etainv_prox_guidance(const float* eps_u, const float* eps_c, float g, int mode, int use_rank, int rank_lo, float rank_w, float thr_fixed,
+                         float* eps_out, const float* x, float a_from, float a_to, float* x_out, float* thr_out, int n_groups,
+                         int rows_per_group, int l, void* stream);
+
 /* ---------------------------------------------------------------- engine */
 typedef struct etainv_engine etainv_engine_t;
 
