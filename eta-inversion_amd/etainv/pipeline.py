@@ -10,7 +10,7 @@ Replaces, for B independent (source, target) pairs at once (the reference handle
   DiffusionInversion.sample batch layout                        reference modules/inversion/diffusion_inversion.py:462-528
   EdictInversion.predict_step_forward / predict_step_backward   reference modules/inversion/edict_inversion.py:393-420 (EdictLoop)
 """
-import ctypes as C
+import functools
 import os
 
 import numpy as np
@@ -18,7 +18,8 @@ import torch
 
 from . import _capi
 from .engine import AttnControl
-from .flops import edict_unet_rows, exit_share, pnp_step_rows
+from .flops import edict_unet_rows, exit_share
+from .plan import FULL, LAYOUTS, plan_backward
 
 NUM_TRAIN = 1000
 
@@ -66,6 +67,45 @@ def attn_layer_selection(L, attn_res=None, attn_from_where=("up", "down")):
     return div, mask
 
 
+class _MaskSource:
+    """The eta mask of one `EtaLoop.sample` call (reference eta_inversion.py:164-201): `static` maps, the raw map of a source at a step, get_mask's tail"""
+
+    def __init__(self, loop, inv, edit_word, edit_word_tgt, gt_mask, ptp):
+        self.loop, self.inv = loop, inv
+        L, B, dev = loop.L, inv["latents"].shape[1], inv["latents"].device
+        self.idx = edit_word.to(dev).long().reshape(B, 1, 1, 1).expand(B, 1, L, L)
+        self.mode = 2 if loop.mask_thres is None or loop.mask_pow is not None or loop.mask_eta != "fwd_mean" else 1   # 2: the map is the per-pixel eta multiplier
+        sources = {loop.mask_eta, loop.mask_dirinv} - {None}
+        if any(sname.startswith("bwd") for sname in sources):                        # maps of the backward-pass store (eta_inversion.py:176-183)
+            assert ptp is not None, "bwd_* masks read the prompt-to-prompt controller's maps"
+            token = lambda word: (word.to(dev).int() + 1).reshape(B, 1).contiguous()
+            self.tok_s, self.tok_t = token(edit_word), token(edit_word_tgt if edit_word_tgt is not None else edit_word)
+            self.map_s, self.map_t = (torch.empty(B, 1, L, L, dtype=torch.float32, device=dev) for _ in range(2))
+        self.static = {}
+        if "gt" in sources:
+            assert gt_mask is not None, "a 'gt' mask source needs the ground-truth mask (B,L,L)"
+            self.static["gt"] = gt_mask.to(dev).float().reshape(B, L, L)
+        if "fwd_mean" in sources:
+            self.static["fwd_mean"] = inv["maps_mean"].gather(1, self.idx).reshape(B, L, L)
+
+    def shaped(self, m):                                                            # get_mask tail, eta_inversion.py:196-201: threshold, then power
+        m = m if self.loop.mask_thres is None else (m > self.loop.mask_thres).to(m.dtype)
+        return (m if self.loop.mask_pow is None else torch.pow(m, self.loop.mask_pow)).contiguous()
+
+    def src_map(self, name, i):                                                     # raw map of one source at backward step i (eta_inversion.py:164-183)
+        loop, (B, _, L, _) = self.loop, self.idx.shape
+        if name in self.static:
+            return self.static[name]
+        if name == "fwd":                                                           # map of THIS timestep (t_bwd[i] == t_fwd[S-1-i])
+            return self.inv["maps_steps"][loop.S - 1 - i].gather(1, self.idx).reshape(B, L, L)
+        if name != "bwd_target":                                                    # average over the i+1 backward steps done, this one included
+            loop.e.word_maps_ex(B, self.tok_s, i + 1, 0, loop.attn_layer_mask, self.map_s)
+        if name != "bwd_source":
+            loop.e.word_maps_ex(B, self.tok_t, i + 1, 1, loop.attn_layer_mask, self.map_t)
+        m = self.map_s if name == "bwd_source" else self.map_t if name == "bwd_target" else torch.maximum(self.map_s, self.map_t)
+        return m.reshape(B, L, L)
+
+
 class EtaLoop:
 
     def __init__(self, engine, S=50, guidance_scale_bwd=7.5, guidance_scale_fwd=1.0, eta=(0.0, 0.4), noise_sample_count=10,
@@ -100,21 +140,15 @@ class EtaLoop:
         self.skip_uncond_fwd = skip_uncond_fwd and self.g_fwd == 1.0 and self.g_fwd_table is None
         if regularizer is not None and regularizer.L != self.L:
             raise ValueError(f"the regulariser was built for {regularizer.L} x {regularizer.L} latents, the engine runs {self.L} x {self.L}")
-        # Backward steps with eta(t) == 0 (the whole ramp-free part of the paper's schedule: 30 of 50 steps with eta [[0.6, 0], [1, 0.7]]): the source
-        # row is REPLAYED from the inversion trajectory (eta_inversion.py:247-249) and its guided noise feeds nothing but the best-of-n choice of a
-        # noise sample that is then multiplied by eta sigma = 0 (:232, :330-375) -- eps(uncond source) is dead work.  Those steps run 3 B UNet rows
-        # [u_t, c_s, c_t] with prompt-to-prompt (the cond source row stays: its attention probabilities are what is injected into the target) and
-        # 2 B rows [u_t, c_t] without an attention coupling (simple editor); MasaCtrl couples u_t to u_s and keeps all four.  The source row then is
-        # x_prev_src itself instead of x + (x_prev_src - x): at most one rounding apart (SURVEY E-11).  Like skip_uncond_fwd an exact identity of the
-        # reference's arithmetic, not an approximation; skip_dead_source_rows=False runs the reference's row count.
-        self.skip_dead_source_rows = skip_dead_source_rows and target_dirinv is None and not _env_on("ETAINV_NO_DEAD_ROW_SKIP")   # (env: A/B switch)
-        # ... and once nothing is injected from the source (no cross replacement, self-replace over: steps >= 30 of 50 with the PIE settings) the cond source
-        # row of such a step leaves the network after the last stored (L/4)^2 cross layer (transformer block 9; etainv_attn_ctrl.src_exit_block): its
-        # noise prediction is unused.  ETAINV_NO_SRC_EXIT=1: A/B switch.
+        # Backward steps with eta(t) == 0 (30 of 50 with the paper's eta [[0.6, 0], [1, 0.7]]) REPLAY the source row from the inversion trajectory (eta_inversion.py:
+        # 247-249); its guided noise only picks a noise sample that is then multiplied by eta sigma = 0 (:232, :330-375), so eps(uncond source) is dead work and those
+        # steps run fewer rows (which ones: etainv.plan).  Like skip_uncond_fwd an identity of the reference's arithmetic, the source row one rounding apart at most
+        # (SURVEY E-11), not an approximation; skip_dead_source_rows=False runs the reference's row count.  The environment variables are A/B switches.
+        self.skip_dead_source_rows = skip_dead_source_rows and target_dirinv is None and not _env_on("ETAINV_NO_DEAD_ROW_SKIP")
+        # ... and the cond source row of such a step leaves the network early once nothing is injected from it (etainv_attn_ctrl.src_exit_block)
         self.src_exit = self.skip_dead_source_rows and not _env_on("ETAINV_NO_SRC_EXIT")
         self.src_exit_9_only = _env_on("ETAINV_SRC_EXIT_9_ONLY")   # A/B: no exit while the self-replace runs
-        # share of a sample-forward's FLOPs a row has run when it leaves after transformer block 9 / 12 (layer walk at THIS latent size:
-        # 0.509 / 0.716 at L = 64, 0.492 / 0.677 at L = 96 where the N^2 self-attention terms weigh more)
+        # share of a sample-forward's FLOPs a row has run when it leaves after transformer block 9 / 12, at THIS latent size (0.509 / 0.716 at L = 64)
         self.SRC_EXIT_SHARE, self.SRC_EXIT_SHARE_12 = exit_share(self.L, 9), exit_share(self.L, 12)
         self.rows_executed = 0                                   # UNet sample-forwards issued by invert / sample since construction (bench accounting)
         self.lib = engine.lib
@@ -164,15 +198,14 @@ class EtaLoop:
                 e.unet(x_in, int(t), ctx, ctrl, out=eps_all)
                 self.rows_executed += rows
                 a_from, a_to = self._alpha(int(t) - self.delta), self._alpha(int(t))   # "sameshift" (scheduling_ddim_inverse.py:127-131)
+                g = float(self.g_fwd_table[int(t)]) if self.g_fwd_table is not None else self.g_fwd
                 if reg is not None:
                     if self.skip_uncond_fwd:                   # one row per image: the noise already is the guided one
                         reg.run(self.lib, None, eps_all, 1.0, eps_reg[j], x_in, a_from, a_to, lat[j + 1], B, st)
                     else:
-                        g = float(self.g_fwd_table[int(t)]) if self.g_fwd_table is not None else self.g_fwd
                         reg.run(self.lib, eps_all[:B], eps_all[B:], g, eps_reg[j], x_in, a_from, a_to, lat[j + 1], B, st)
                 else:
                     if not self.skip_uncond_fwd:
-                        g = float(self.g_fwd_table[int(t)]) if self.g_fwd_table is not None else self.g_fwd
                         _capi.check(self.lib.etainv_cfg_combine(_capi.ptr(eps_all[:B]), _capi.ptr(eps_all[B:]), g, _capi.ptr(eps), n,
                                                                 _capi.F32, st))
                     _capi.check(self.lib.etainv_ddim_step(_capi.ptr(x_in), _capi.ptr(eps), a_from, a_to, _capi.ptr(lat[j + 1]), n, _capi.F32, st))
@@ -194,165 +227,76 @@ class EtaLoop:
         leading backward steps with the feature / the Q,K injection (reference modules/utils/pnp.py:50-54: int(S * 0.8), int(S * 0.5)); ctx_tgt[:, 0] then
         is the negative-prompt row.  At most one of ptp / masactrl / pnp.  Returns latents (2B,4,L,L) [src.., tgt..].
         teacher (S,2B,4,L,L), tests only: step i starts from teacher[i] (see invert)."""
-        e, S, L = self.e, self.S, self.L
-        lat_inv = inv["latents"]
-        B = lat_inv.shape[1]
-        dev = lat_inv.device
+        e, S, L, lat_inv = self.e, self.S, self.L, inv["latents"]
+        B, dev = lat_inv.shape[1], lat_inv.device
         if sum(c is not None for c in (ptp, masactrl, pnp)) > 1:
             raise ValueError("ptp, masactrl and pnp are exclusive: one attention coupling per backward pass")
-        ctx = torch.cat([ctx_src[:, 0], ctx_tgt[:, 0], ctx_src[:, 1], ctx_tgt[:, 1]]).contiguous().float()   # [u_s,u_t,c_s,c_t] x B
-        ctx_p = eps_p = None
-        if pnp is not None:
-            # PnPUnetForward (pnp.py:130-146): the cond source row is cut, the network runs [u_s, u_t, c_t] and the uncond source noise stands in for the cond
-            # source noise -- the guided source noise u + g (u - u) is u_s itself
-            conv_steps, qk_steps = int(pnp[0]), int(pnp[1])
-            ctx_p = torch.cat([ctx_src[:, 0], ctx_tgt[:, 0], ctx_tgt[:, 1]]).contiguous().float()                # [u_s,u_t,c_t] x B
-            eps_p = torch.empty(3 * B, 4, L, L, dtype=torch.float32, device=dev)
+        steps = plan_backward(S, self.t_bwd, self.etas, self.ac, self.delta, L, B, self.skip_dead_source_rows, self.src_exit, self.src_exit_9_only, ptp, masactrl, pnp)
+        roles = {"u_s": ctx_src[:, 0], "u_t": ctx_tgt[:, 0], "c_s": ctx_src[:, 1], "c_t": ctx_tgt[:, 1]}
+
+        @functools.lru_cache(maxsize=None)
+        def buffers(name):                                      # (context rows, noise rows, their eu and ec groups) of a layout, built when it first runs
+            lay = LAYOUTS[name]
+            eps = torch.empty(len(lay.roles) * B, 4, L, L, dtype=torch.float32, device=dev)
+            return torch.cat([roles[r] for r in lay.roles]).contiguous().float(), eps, eps[lay.eu * B:(lay.eu + 1) * B], eps[lay.ec * B:(lay.ec + 1) * B]
+        eps_all = buffers(FULL)[1]                                                 # the eta step reads the reference's four row groups, whatever ran
         x = torch.cat([lat_inv[S], lat_inv[S]]).contiguous()
         x_new = torch.empty_like(x)
-        eps_all = torch.empty(4 * B, 4, L, L, dtype=torch.float32, device=dev)
-        best = torch.zeros(B, dtype=torch.int32, device=dev)
-        scratch = torch.empty(B * 16 * 64, dtype=torch.float32, device=dev)
-        mask_map, mask_mode = None, int(self.use_mask)
-        src_map = shaped = None
-        if self.use_mask:
-            idx = edit_word.to(dev).long().reshape(B, 1, 1, 1).expand(B, 1, L, L)
-            final = self.mask_thres is None or self.mask_pow is not None or self.mask_eta != "fwd_mean"
-            mask_mode = 2 if final else 1                                           # 2: the map is the per-pixel eta multiplier
-            sources = {self.mask_eta, self.mask_dirinv} - {None}
-            if any(sname.startswith("bwd") for sname in sources):                    # maps of the backward-pass store (eta_inversion.py:176-183)
-                assert ptp is not None, "bwd_* masks read the prompt-to-prompt controller's maps"
-                tok_s = (edit_word.to(dev).int() + 1).reshape(B, 1).contiguous()
-                tok_t = ((edit_word_tgt if edit_word_tgt is not None else edit_word).to(dev).int() + 1).reshape(B, 1).contiguous()
-                map_s = torch.empty(B, 1, L, L, dtype=torch.float32, device=dev)
-                map_t = torch.empty(B, 1, L, L, dtype=torch.float32, device=dev)
-            static = {}
-            if "gt" in sources:
-                assert gt_mask is not None, "a 'gt' mask source needs the ground-truth mask (B,L,L)"
-                static["gt"] = gt_mask.to(dev).float().reshape(B, L, L)
-            if "fwd_mean" in sources:
-                static["fwd_mean"] = inv["maps_mean"].gather(1, idx).reshape(B, L, L)
-
-            def shaped(m):                                                          # get_mask tail, eta_inversion.py:196-201
-                if self.mask_thres is not None:
-                    m = (m > self.mask_thres).to(m.dtype)
-                if self.mask_pow is not None:
-                    m = torch.pow(m, self.mask_pow)
-                return m.contiguous()
-
-            def src_map(name, i):                                                   # raw map of one source at backward step i (eta_inversion.py:164-183)
-                if name in static:
-                    return static[name]
-                if name == "fwd":                                                   # map of THIS timestep (t_bwd[i] == t_fwd[S-1-i])
-                    return inv["maps_steps"][S - 1 - i].gather(1, idx).reshape(B, L, L)
-                if name != "bwd_target":                                            # average over the i+1 backward steps done, this one included
-                    e.word_maps_ex(B, tok_s, i + 1, 0, self.attn_layer_mask, map_s)
-                if name != "bwd_source":
-                    e.word_maps_ex(B, tok_t, i + 1, 1, self.attn_layer_mask, map_t)
-                m = map_s if name == "bwd_source" else map_t if name == "bwd_target" else torch.maximum(map_s, map_t)
-                return m.reshape(B, L, L)
+        best, scratch = torch.zeros(B, dtype=torch.int32, device=dev), torch.empty(B * 16 * 64, dtype=torch.float32, device=dev)
+        masks = _MaskSource(self, inv, edit_word, edit_word_tgt, gt_mask, ptp) if self.use_mask else None
+        mask_map, mask_mode = None, (masks.mode if masks is not None else 0)
         if ptp is not None:
             if e.map_div != 4:
                 e.maps_configure(4)                                                  # LocalBlend and the bwd_* sources read the (L/4)^2 layers
             else:
                 e.maps_reset()
-        ctx3 = eps3 = ctx3x = eps3x = None
         losses = torch.zeros(B, self.n_cand, dtype=torch.float32, device=dev) if trace is not None else None   # per-candidate losses of the best-of-n step (traces only)
         eps_t = torch.empty(B, 4, L, L, dtype=torch.float32, device=dev)
         st = _capi.stream_ptr()
-        with e.cached_context():                               # one unchanged context tensor for all S calls
-            for i, t in enumerate(self.t_bwd):
-                t = int(t)
+        with e.cached_context():                               # the context tensor of a layout stays unchanged over all its calls
+            for i, s in enumerate(steps):
+                lay = LAYOUTS[s.layout]
                 ctrl = None
-                if ptp is not None:
-                    live = bool(ptp.cross_active[i])
-                    ctrl = AttnControl(mode=_capi.ATTN_PTP, n_img=B, store_maps=True, mapper=ptp.mapper if live else None, alphas=ptp.alphas,
-                                       replace_mat=ptp.replace_mat if live else None, equalizer=ptp.equalizer, cross_alpha=ptp.cross_alpha[i],
-                                       self_replace_active=ptp.self_lo <= i < ptp.self_hi, self_max_tokens=(L // 2) ** 2)
-                elif masactrl is not None:
-                    ctrl = AttnControl(mode=_capi.ATTN_MASA, n_img=B, masa_active=masactrl[0] <= i < 50, masa_first_block=masactrl[1])
-                elif pnp is not None:
-                    ctrl = AttnControl(mode=_capi.ATTN_PNP, n_img=B, pnp_qk_active=i < qk_steps, pnp_conv_active=i < conv_steps)
+                if lay.ctrl and ptp is not None:
+                    ctrl = AttnControl(mode=_capi.ATTN_PTP, n_img=B, store_maps=True, mapper=ptp.mapper if s.edit else None, alphas=ptp.alphas,
+                                       replace_mat=ptp.replace_mat if s.edit else None, equalizer=ptp.equalizer, cross_alpha=ptp.cross_alpha[i],
+                                       self_replace_active=s.self_replace_active, self_max_tokens=(L // 2) ** 2)
+                    ctrl.c.first_row, ctrl.c.src_exit_block = s.first_row, s.src_exit_block
+                elif lay.ctrl and masactrl is not None:
+                    ctrl = AttnControl(mode=_capi.ATTN_MASA, n_img=B, masa_active=s.masa_active, masa_first_block=masactrl[1])
+                elif lay.ctrl and pnp is not None:
+                    ctrl = AttnControl(mode=_capi.ATTN_PNP, n_img=B, pnp_qk_active=s.pnp_qk_active, pnp_conv_active=s.pnp_conv_active)
                 if teacher is not None:
                     x.copy_(teacher[i])
-                p = t - self.delta
-                a_t, a_p = float(self.ac[t]), (float(self.ac[p]) if p >= 0 else float(self.ac[0]))
-                var = (1 - a_p) / (1 - a_t) * (1 - a_t / a_p)
-                if self.skip_dead_source_rows and float(self.etas[t]) == 0.0 and masactrl is None:
-                    # eta == 0: no eps(uncond source) -- rows [u_t, c_s, c_t] over latents [tgt, src] (ptp) or [u_t, c_t] over [tgt] (no coupling)
-                    if ptp is not None and not live and self.src_exit and not (self.src_exit_9_only and ptp.self_lo <= i < ptp.self_hi):
-                        # no cross replacement any more: the cond source row only feeds the AttentionStore of the five (L/4)^2 cross layers (LocalBlend /
-                        # bwd_* masks; last one = block 9) and, while the self-replace runs, the (L/2)^2-token self-attentions (last one = block 12) --
-                        # rows [u_t, c_t, c_s], c_s leaves after that block
-                        if ctx3x is None:
-                            ctx3x = torch.cat([ctx_tgt[:, 0], ctx_tgt[:, 1], ctx_src[:, 1]]).contiguous().float()
-                            eps3x = torch.empty(3 * B, 4, L, L, dtype=torch.float32, device=dev)
-                        self_on = ptp.self_lo <= i < ptp.self_hi
-                        ctrl.c.first_row, ctrl.c.src_exit_block = B, 12 if self_on else 9
-                        e.unet(torch.cat([x[B:], x[B:], x[:B]]), t, ctx3x, ctrl, out=eps3x)
-                        eu, ec = eps3x[:B], eps3x[B:2 * B]
-                        rows_out, layout = eps3x[:2 * B], "u_t,c_t"                    # (the exited c_s rows have no output)
-                        self.rows_executed += 2 * B + B * (self.SRC_EXIT_SHARE_12 if self_on else self.SRC_EXIT_SHARE)   # (share of the UNet's FLOPs the exited rows ran)
-                    elif ptp is not None:
-                        if ctx3 is None:
-                            ctx3 = torch.cat([ctx_tgt[:, 0], ctx_src[:, 1], ctx_tgt[:, 1]]).contiguous().float()
-                            eps3 = torch.empty(3 * B, 4, L, L, dtype=torch.float32, device=dev)
-                        ctrl.c.first_row = B
-                        e.unet(torch.cat([x[B:], x[:B]]), t, ctx3, ctrl, out=eps3)
-                        eu, ec = eps3[:B], eps3[2 * B:]
-                        rows_out, layout = eps3, "u_t,c_s,c_t"
-                        self.rows_executed += 3 * B
-                    elif pnp is not None and i < max(conv_steps, qk_steps):
-                        # an injection is live: the target rows read the u_s row inside the network, so it runs although nothing reads its noise
-                        e.unet(torch.cat([x[:B], x[B:], x[B:]]), t, ctx_p, ctrl, out=eps_p)
-                        eu, ec = eps_p[B:2 * B], eps_p[2 * B:]
-                        rows_out, layout = eps_p, "u_s,u_t,c_t"
-                        self.rows_executed += pnp_step_rows(i, B, conv_steps, qk_steps, True)
-                    else:
-                        if ctx3 is None:
-                            ctx3 = torch.cat([ctx_tgt[:, 0], ctx_tgt[:, 1]]).contiguous().float()
-                            eps3 = torch.empty(2 * B, 4, L, L, dtype=torch.float32, device=dev)
-                        e.unet(x[B:], t, ctx3, None, out=eps3)
-                        eu, ec = eps3[:B], eps3[B:]
-                        rows_out, layout = eps3, "u_t,c_t"
-                        self.rows_executed += 2 * B
-                    n_t = B * 4 * L * L
-                    _capi.check(self.lib.etainv_cfg_combine(_capi.ptr(eu), _capi.ptr(ec), self.g_bwd, _capi.ptr(eps_t), n_t, _capi.F32, st))
-                    _capi.check(self.lib.etainv_ddim_eta_step(_capi.ptr(x[B:]), _capi.ptr(eps_t), 0.0, None, 0, None, a_t, a_p, var, B, 4, L * L,
-                                                              _capi.ptr(x_new[B:]), _capi.F32, st))
-                    x_new[:B].copy_(lat_inv[S - 1 - i])                                 # the replayed source row
+                ctx, eps, eu, ec = buffers(s.layout)
+                lat = x if lay.latents == ("src", "tgt") else x[B:] if lay.latents == ("tgt",) else torch.cat([x[:B] if side == "src" else x[B:] for side in lay.latents])
+                e.unet(lat, s.t, ctx, ctrl, out=eps)
+                self.rows_executed += B * s.cost
+                if s.replay:                                                            # eta == 0: plain DDIM step of the target, the source row is replayed
+                    _capi.check(self.lib.etainv_cfg_combine(_capi.ptr(eu), _capi.ptr(ec), self.g_bwd, _capi.ptr(eps_t), B * 4 * L * L, _capi.F32, st))
+                    _capi.check(self.lib.etainv_ddim_eta_step(_capi.ptr(x[B:]), _capi.ptr(eps_t), 0.0, None, 0, None, s.a_t, s.a_p, s.var, B, 4, L * L, _capi.ptr(x_new[B:]), _capi.F32, st))
+                    x_new[:B].copy_(lat_inv[S - 1 - i])
                     best.zero_()                                                        # (the reference's argmin over NaN losses: index 0)
-                    x, x_new = x_new, x
-                    if ptp is not None and ptp.blend_alpha is not None and (i + 1) > int(0.2 * S):
-                        e.local_blend(x, B, ptp.blend_alpha, 0.3)
-                    if trace is not None:
-                        # the rows this step executed, with their layout (B rows per name); "eps_all" (the 4 B-row layout) does not exist here
-                        trace.append({"t": t, "latent": x.clone(), "best": best.clone(), "eps_all": None, "eps_rows": rows_out.clone(), "layout": layout})
-                    continue
-                if pnp is not None:
-                    e.unet(torch.cat([x[:B], x[B:], x[B:]]), t, ctx_p, ctrl, out=eps_p)
-                    eps_all.view(4, B, 4, L, L).copy_(eps_p.view(3, B, 4, L, L)[[0, 1, 0, 2]])     # rows [0, 1, 0, 2] (pnp.py:146)
-                    self.rows_executed += pnp_step_rows(i, B, conv_steps, qk_steps, False)
                 else:
-                    e.unet(x, t, ctx, ctrl, out=eps_all)
-                    self.rows_executed += 4 * B
-                dmap = None
-                if self.use_mask:
-                    raw = src_map(self.mask_eta, i)
-                    mask_map = shaped(raw) if mask_mode == 2 else raw.contiguous()      # mode 1: the kernel thresholds the raw forward-mean map
-                    if self.target_dirinv is not None and self.mask_dirinv is not None:  # 1 - shaped map of the mask_dirinv source (eta_inversion.py:234-256)
-                        dmap = (1.0 - shaped(raw if self.mask_dirinv == self.mask_eta else src_map(self.mask_dirinv, i))).contiguous()
-                _capi.check(self.lib.etainv_eta_backward_step_ex(
-                    _capi.ptr(x), _capi.ptr(eps_all), self.g_bwd, _capi.ptr(lat_inv[S - 1 - i]), _capi.ptr(noise[i]), self.n_cand,
-                    float(self.etas[t]), _capi.ptr(mask_map), float(self.mask_thres or 0.0), mask_mode, a_t, a_p, var, B, 4, L * L,
-                    _capi.ptr(x_new), None, _capi.ptr(best), _capi.ptr(losses), _capi.ptr(scratch), _capi.F32, float(self.target_dirinv or 0.0), _capi.ptr(dmap), st))
+                    if pnp is not None:                                                 # u_s stands in for the cut c_s: rows [0, 1, 0, 2] (pnp.py:146)
+                        eps_all.view(4, B, 4, L, L).copy_(eps.view(3, B, 4, L, L)[[0, 1, 0, 2]])
+                    dmap = None
+                    if masks is not None:
+                        raw = masks.src_map(self.mask_eta, i)
+                        mask_map = masks.shaped(raw) if mask_mode == 2 else raw.contiguous()   # mode 1: the kernel thresholds the raw forward-mean map
+                        if self.target_dirinv is not None and self.mask_dirinv is not None:   # 1 - shaped map of the mask_dirinv source (eta_inversion.py:234-256)
+                            dmap = (1.0 - masks.shaped(raw if self.mask_dirinv == self.mask_eta else masks.src_map(self.mask_dirinv, i))).contiguous()
+                    _capi.check(self.lib.etainv_eta_backward_step_ex(
+                        _capi.ptr(x), _capi.ptr(eps_all), self.g_bwd, _capi.ptr(lat_inv[S - 1 - i]), _capi.ptr(noise[i]), self.n_cand,
+                        s.eta, _capi.ptr(mask_map), float(self.mask_thres or 0.0), mask_mode, s.a_t, s.a_p, s.var, B, 4, L * L,
+                        _capi.ptr(x_new), None, _capi.ptr(best), _capi.ptr(losses), _capi.ptr(scratch), _capi.F32, float(self.target_dirinv or 0.0), _capi.ptr(dmap), st))
                 x, x_new = x_new, x
-                if ptp is not None and ptp.blend_alpha is not None and (i + 1) > int(0.2 * S):
+                if s.blend:
                     e.local_blend(x, B, ptp.blend_alpha, 0.3)                       # LocalBlend, reference ptp.py:31-47
                 if trace is not None:
-                    trace.append({"t": t, "latent": x.clone(), "best": best.clone(), "eps_all": eps_all.clone(),
-                                  "eps_rows": (eps_all if pnp is None else eps_p).clone(),
-                                  "layout": "u_s,u_t,c_s,c_t" if pnp is None else "u_s,u_t,c_t", "losses": losses.clone()})
+                    # "eps_rows": the rows with an output this step ran, B per name of "layout"; "eps_all" (4 B rows) and "losses": eta steps only
+                    trace.append({"t": s.t, "latent": x.clone(), "best": best.clone(), "eps_all": None if s.replay else eps_all.clone(),
+                                  "eps_rows": eps[:lay.n_out * B].clone(), "layout": s.trace_layout, **({} if s.replay else {"losses": losses.clone()})})
         return x
 
 

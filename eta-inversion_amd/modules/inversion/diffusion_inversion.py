@@ -35,6 +35,18 @@ class DiffusionInversion:
         self.controller.end()
         self.controller = ControllerEmpty()
 
+    @staticmethod
+    def _plain_ddim(scheduler, dict_type=False, unnamed=True) -> bool:
+        """Is this scheduler argument -- None, a name or a configuring dict -- the plain "ddim"?  A dict configures a scheduler of its own and is not
+        plain, unless `dict_type` lets its "type" field answer; `unnamed` is the answer for None and for a dict without that field."""
+        if dict_type and isinstance(scheduler, dict):
+            scheduler = scheduler.get("type")
+        return unnamed if scheduler is None else scheduler == "ddim"
+
+    def _unwatched(self, controllers=None) -> bool:
+        """no controller (default: the one in use) watches the steps and force_per_step, an attribute, is not set: a fused loop may stand in"""
+        return all(isinstance(c, ControllerEmpty) for c in controllers or [self.controller]) and not getattr(self, "force_per_step", False)
+
     def pbar(self, it, **kwargs):
         if self.verbose:
             from tqdm import tqdm

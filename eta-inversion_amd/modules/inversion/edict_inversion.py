@@ -114,10 +114,9 @@ class EdictInversion(DiffusionInversion):
             self.controller = EdictController(ControllerEmpty())
 
     def create_schedulers(self, model, scheduler, num_inference_steps, scheduler_inv_kwargs=None):
-        name = scheduler if isinstance(scheduler, str) else scheduler.get("type")
-        if name != "ddim":
+        if not self._plain_ddim(scheduler, dict_type=True, unnamed=False):
             # (the reference throws the inverse scheduler away and wraps whatever backward scheduler it got as if it were DDIM, :279-286)
-            raise NotImplementedError(f"edict steps both passes with its own DDIM-form update; scheduler '{name}' is not built for it (use 'ddim')")
+            raise NotImplementedError(f"edict steps both passes with its own DDIM-form update; scheduler '{scheduler}' is not built for it (use 'ddim')")
         sched, bwd, _ = super().create_schedulers(model, scheduler, num_inference_steps, scheduler_inv_kwargs)
         return sched, EdictScheduler(bwd), EdictSchedulerInverse(bwd)
 
@@ -194,8 +193,7 @@ class EdictInversion(DiffusionInversion):
     # ------------------------------------------------------------------ loops
     def _fast(self) -> bool:
         """the batched device loop serves the passes that no controller watches (force_per_step, an attribute, keeps the per-step path)"""
-        plain = all(isinstance(c, ControllerEmpty) for c in self.controller.controllers)
-        return plain and not getattr(self, "force_per_step", False)
+        return self._unwatched(self.controller.controllers)              # (one copy of the controller per pair member)
 
     def diffusion_forward(self, latent, context, guidance_scale_fwd=None):
         scale = guidance_scale_fwd or self.guidance_scale_fwd

@@ -37,9 +37,8 @@ class EtaInversion(DiffusionInversion):
         if isinstance(guidance_scale_fwd, (tuple, list)):                  # per-timestep table (reference :108-110): handled by the native loop
             assert len(guidance_scale_fwd) == 2
             g_fwd_pair, guidance_scale_fwd = tuple(guidance_scale_fwd), None
-        name = scheduler if isinstance(scheduler, str) or scheduler is None else scheduler.get("type")
-        if name not in (None, "ddim"):                                     # the backward step passes eta / variance_noise (reference :245): DDIM only
-            raise NotImplementedError(f"etainv / dirinv step the backward pass with DDIM(eta); scheduler '{name}' has no eta (use diffinv for 'dpm')")
+        if not self._plain_ddim(scheduler, dict_type=True):                # the backward step passes eta / variance_noise (reference :245): DDIM only
+            raise NotImplementedError(f"etainv / dirinv step the backward pass with DDIM(eta); scheduler '{scheduler}' has no eta (use diffinv for 'dpm')")
         super().__init__(model, scheduler, num_inference_steps, guidance_scale_bwd, guidance_scale_fwd, verbose)
         self._g_fwd_pair = g_fwd_pair
         if eta_start is not None:
@@ -186,14 +185,18 @@ class EtaInversion(DiffusionInversion):
         new_latent = self.controller.end_step(latent=res["latent"], noise_pred=res["noise_pred"], t=t)
         return new_latent, res["noise_pred"]
 
+    def _step_operands(self, t: int, device):
+        """(a_t, a_p, var) of backward timestep t from scheduler_bwd, and the best / losses / scratch buffers of the fused eta step on one pair"""
+        sch = self.scheduler_bwd
+        p = t - sch.config.num_train_timesteps // self.num_inference_steps
+        best = torch.zeros(1, dtype=torch.int32, device=device)
+        losses = torch.zeros(1, self.noise_sample_count, dtype=torch.float32, device=device)
+        return (sch._alpha(t), sch._alpha(p), sch._get_variance(t, p)), best, losses, torch.empty(16 * 64, dtype=torch.float32, device=device)
+
     def _fused_eta_step(self, latent_prev, latent, t, eps_all, generator, mask, edit_word_idx, guidance_scale_bwd=None):
         """etainv_eta_backward_step_ex on one pair: `eps_all` = raw UNet output rows [u_s,u_t,c_s,c_t], `latent` = [source, target]."""
-        t = int(t)
-        S, L = self.num_inference_steps, self.L
+        t, L = int(t), self.L
         cand = self.sample_variance_noise(self.noise_sample_count, generator).reshape(self.noise_sample_count, 4, L, L).float().contiguous()
-        sch = self.scheduler_bwd
-        p = t - sch.config.num_train_timesteps // S
-        a_t, a_p, var = sch._alpha(t), sch._alpha(p), sch._get_variance(t, p)
         m_eta = self.get_mask("mask_eta", mask, t, edit_word_idx) if self.mask_mode_cfg is not None else None
         use_mask = self.mask_mode_cfg is not None
         if use_mask and m_eta is None:                                     # mask_eta None inside a mask_mode_cfg: eta everywhere (:239-240)
@@ -201,9 +204,7 @@ class EtaInversion(DiffusionInversion):
         mask_map = m_eta.float().reshape(1, L, L).contiguous() if use_mask else None
         x = latent.float().contiguous()
         out_x, out_eps = torch.empty_like(x), torch.empty_like(x)
-        best = torch.zeros(1, dtype=torch.int32, device=x.device)
-        losses = torch.zeros(1, self.noise_sample_count, dtype=torch.float32, device=x.device)
-        scratch = torch.empty(16 * 64, dtype=torch.float32, device=x.device)
+        (a_t, a_p, var), best, losses, scratch = self._step_operands(t, x.device)
         tdir = (self.mask_mode_cfg or {}).get("target_dirinv")
         dmap = None
         if tdir is not None and self.mask_mode_cfg["mask_dirinv"] is not None:
@@ -228,19 +229,13 @@ class EtaInversion(DiffusionInversion):
         """Reference signature and result keys (eta_inversion.py:330-375): `latent` = the source row (1,4,L,L), `noise_pred` = its GUIDED
         noise.  Best-of-n selection runs in the fused kernel (fed with u = c = noise_pred so that its CFG combine is the identity); the
         chosen candidate is gathered on the device (no host sync)."""
-        tt = int(t)
-        S, L = self.num_inference_steps, self.L
+        tt, L = int(t), self.L
         cand5 = self.sample_variance_noise(self.noise_sample_count, generator)                     # (n,1,4,L,L)
         cand = cand5.reshape(self.noise_sample_count, 4, L, L).float().contiguous()
-        sch = self.scheduler_bwd
-        p = tt - sch.config.num_train_timesteps // S
-        a_t, a_p, var = sch._alpha(tt), sch._alpha(p), sch._get_variance(tt, p)
         x = torch.cat([latent, latent]).float().contiguous()
         eps4 = torch.cat([noise_pred] * 4).float().contiguous()
         out_x = torch.empty_like(x)
-        best = torch.zeros(1, dtype=torch.int32, device=x.device)
-        losses = torch.zeros(1, self.noise_sample_count, dtype=torch.float32, device=x.device)
-        scratch = torch.empty(16 * 64, dtype=torch.float32, device=x.device)
+        (a_t, a_p, var), best, losses, scratch = self._step_operands(tt, x.device)
         eta = float(self.etas[tt])
         _capi.check(_capi.load().etainv_eta_backward_step(
             _capi.ptr(x), _capi.ptr(eps4), 1.0, _capi.ptr(latent_prev.float().contiguous()), _capi.ptr(cand), self.noise_sample_count, eta,

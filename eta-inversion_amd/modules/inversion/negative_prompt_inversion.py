@@ -15,7 +15,6 @@ import torch
 
 from etainv import _capi
 from etainv.pipeline import ProximalGuidance
-from ..editing.controller import ControllerEmpty
 from .diffusion_inversion import DiffusionInversion
 
 
@@ -27,7 +26,7 @@ class NegativePromptInversion(DiffusionInversion):
                                       "backward step is one etainv_prox_guidance launch; built inverters: etainv, dirinv, edict, regdiffinv, npi, "
                                       "proxnpi, diffinv")
         super().__init__(model, scheduler, num_inference_steps, guidance_scale_bwd, guidance_scale_fwd, verbose)
-        self._ddim = (scheduler or "ddim") == "ddim"            # the fused launch steps with the plain DDIM scheduler (a dict configures another one)
+        self._ddim = self._plain_ddim(scheduler or None)        # the fused launch steps with the plain DDIM scheduler (a dict configures another one)
         self.L = model.engine.L
         self._guidance = self._make_guidance()
 
@@ -70,7 +69,7 @@ class NegativePromptInversion(DiffusionInversion):
     # ------------------------------------------------------------------ loops
     def _fast(self) -> bool:
         """the fused step serves the passes that no controller watches (force_per_step, an attribute, keeps the per-step path)"""
-        return isinstance(self.controller, ControllerEmpty) and self._ddim and not getattr(self, "force_per_step", False)
+        return self._ddim and self._unwatched()
 
     def diffusion_backward(self, latent: torch.Tensor, context: torch.Tensor, inv_result: Dict[str, Any]) -> torch.Tensor:
         """(:17-23) at step i every unconditional row of the context is inv_result["uncond_embeddings"][i] -- in a copy of `context`"""

@@ -12,7 +12,6 @@ import torch.nn.functional as F
 
 from etainv import _capi
 from etainv.pipeline import EtaLoop, NoiseRegularizer, regdiff_level_sizes
-from ..editing.controller import ControllerEmpty
 from .diffusion_inversion import DiffusionInversion
 
 
@@ -24,8 +23,7 @@ class RegularizedDiffusionInversion(DiffusionInversion):
         if lambda_ac > 0 and num_reg_steps > 0 and num_ac_rolls <= 0:
             raise ValueError(f"num_ac_rolls must be positive when lambda_ac > 0, got {num_ac_rolls}")
         self.lambda_ac, self.lambda_kl, self.num_reg_steps, self.num_ac_rolls = lambda_ac, lambda_kl, num_reg_steps, num_ac_rolls
-        name = (scheduler or "ddim") if not isinstance(scheduler, dict) else scheduler.get("type")
-        self._ddim = name == "ddim" and not isinstance(scheduler, dict)             # the batched loop steps with the plain DDIM inverse scheduler
+        self._ddim = not isinstance(scheduler, dict) and self._plain_ddim(scheduler or None)   # the batched loop steps with the plain DDIM inverse scheduler
         self.L = model.engine.L
         self._reg = NoiseRegularizer(self.L, lambda_ac, lambda_kl, num_reg_steps, num_ac_rolls, device=model.device)
         # forward guidance linspace(2, 1, 1000)[t], whatever scale is passed (:119-120)
@@ -85,7 +83,7 @@ class RegularizedDiffusionInversion(DiffusionInversion):
     # ------------------------------------------------------------------ loops
     def _fast(self) -> bool:
         """the batched device loop serves the passes that no controller watches (force_per_step, an attribute, keeps the per-step path)"""
-        return isinstance(self.controller, ControllerEmpty) and self._ddim and not getattr(self, "force_per_step", False)
+        return self._ddim and self._unwatched()
 
     def diffusion_forward(self, latent, context, guidance_scale_fwd=None):
         n = latent.shape[0]
