@@ -1,0 +1,128 @@
+#!/usr/bin/env python3
+"""Metrics of a finished eval.py sweep (reference compute_metrics.py:20-126).
+
+    python compute_metrics.py --data_path data/eval/PIE-Bench_v1 --output result/pie_etainv_ptp [--metric mse psnr ssim msssim]
+                              [--batch 32] [--device cuda|cpu] [--size 512] [--limit N] [--categories 1_change_object ...]
+
+Reads the layout eval.py writes, `<output>/imgs/{i:04d}_{source}_{target}.png`, next to the data set's source images.  Kept from the reference:
+one `<output>/metrics/<name>.yaml` per metric, {name, mean, results: [{value, file}]}; a metric whose yaml exists is skipped (the file is
+created exclusively before any work, so two runs never compute the same metric); a sample whose source or edited file is missing is skipped
+with a message; a sample whose metric raises gets nan; both images go through StablePreprocess(size, center_crop=True).  Different by design:
+samples are processed --batch at a time, all wanted metrics of a batch in one `image_metrics` call, and the default metric list is the four
+that are built (EditMetric refuses the others by name)."""
+import argparse
+import sys
+from pathlib import Path
+
+import torch
+import yaml
+
+HERE = Path(__file__).resolve().parent
+sys.path.insert(0, str(HERE))
+from dataset.pie_bench_data import PieBenchData, edit_image_name  # noqa: E402
+from metrics import EditMetric, image_metrics  # noqa: E402
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description="image metrics of the PNGs an eval.py sweep wrote")
+    ap.add_argument("--data_path", required=True)
+    ap.add_argument("--output", required=True, help="the sweep's --output directory (holds imgs/; metrics/ is written next to it)")
+    ap.add_argument("--metric", nargs="+", default=None, choices=EditMetric.get_available_metrics(), metavar="",
+                    help="metric(s) to compute; default: the built ones (%s)" % " ".join(EditMetric.get_built_metrics()))
+    ap.add_argument("--batch", type=int, default=32, help="image pairs per image_metrics call")
+    ap.add_argument("--device", default=None, choices=["cuda", "cpu"], help="default: cuda when there is one")
+    ap.add_argument("--size", type=int, default=512)
+    ap.add_argument("--limit", type=int, default=None)
+    ap.add_argument("--categories", nargs="+", default=None)
+    return ap.parse_args(argv)
+
+
+def _claim(metric_dir: Path, metrics):
+    """the metrics whose yaml this run creates (exclusive create, reference :44-51), with their files"""
+    mine = []
+    for m in metrics:
+        f = metric_dir / f"{m}.yaml"
+        try:
+            open(f, "x").close()
+        except FileExistsError:
+            print(f"skipping {f}")
+            continue
+        mine.append((m, f))
+    return mine
+
+
+def _values(names, edits, sources):
+    """{name: [float per pair]}: one call for the batch; if it raises, pair by pair and metric by metric, nan where that raises"""
+    try:
+        out = image_metrics(torch.cat(edits), torch.cat(sources), (-1, 1), names)
+        return {n: [float(v) for v in out[n].cpu()] for n in names}
+    except Exception:
+        pass
+    vals = {n: [] for n in names}
+    for e, s in zip(edits, sources):
+        for n in names:
+            try:
+                vals[n].append(float(image_metrics(e, s, (-1, 1), (n,))[n][0]))
+            except Exception as exc:
+                print(f"{n}: nan because of {exc}")
+                vals[n].append(float("nan"))
+    return vals
+
+
+@torch.no_grad()
+def main(argv=None):
+    a = parse_args(argv)
+    device = a.device or ("cuda" if torch.cuda.is_available() else "cpu")
+    metrics = [EditMetric(m, input_range=(-1, 1), device=device) for m in (a.metric or EditMetric.get_built_metrics())]
+    metric_dir = Path(a.output) / "metrics"
+    metric_dir.mkdir(parents=True, exist_ok=True)
+    mine = _claim(metric_dir, metrics)
+    if not mine:
+        return
+    names = [str(m) for m, _ in mine]
+    from modules.models import StablePreprocess
+    preproc = StablePreprocess(device, size=a.size, center_crop=True)
+    data = PieBenchData(a.data_path, skip_img_load=True, limit=a.limit, categories=a.categories)
+    results = {n: [] for n in names}
+
+    def flush(stems, edits, sources):
+        if not stems:
+            return
+        vals = _values(names, edits, sources)
+        for (m, _), n in zip(mine, names):
+            m.metric.losses.extend(vals[n])                      # what EditMetric.update records, for the whole batch
+            results[n].extend({"value": v, "file": stem} for v, stem in zip(vals[n], stems))
+
+    stems, edits, sources = [], [], []
+    for i in range(len(data)):
+        s = data[i]
+        edit_file = Path(a.output) / "imgs" / f"{edit_image_name(i, s['source_prompt'], s['edit']['target_prompt'])}.png"
+        if not Path(s["image_file"]).exists() or not edit_file.exists():
+            print(f"Skipping {edit_file}")
+            continue
+        try:
+            e, src = preproc(edit_file), preproc(s["image_file"])
+        except Exception as exc:                                 # an unreadable file: the sample's metrics "raise" (reference :97-107)
+            print(f"Skipping {s['image_file']} because of {exc}")
+            flush(stems, edits, sources)                         # (keeps the results in data-set order)
+            stems, edits, sources = [], [], []
+            for (m, _), n in zip(mine, names):
+                m.metric.losses.append(float("nan"))
+                results[n].append({"value": float("nan"), "file": edit_file.stem})
+            continue
+        stems.append(edit_file.stem)
+        edits.append(e)
+        sources.append(src)
+        if len(stems) == a.batch:
+            flush(stems, edits, sources)
+            stems, edits, sources = [], [], []
+    flush(stems, edits, sources)
+    for (m, f), n in zip(mine, names):
+        res = {"name": n, "mean": m.compute()[0] if results[n] else float("nan"), "results": results[n]}
+        with open(f, "w") as fh:
+            yaml.dump(res, fh, Dumper=getattr(yaml, "CSafeDumper", yaml.SafeDumper))
+        print(f"{n}: mean {res['mean']} over {len(results[n])} samples -> {f}")
+
+
+if __name__ == "__main__":
+    main()

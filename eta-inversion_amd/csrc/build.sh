@@ -3,7 +3,7 @@
 set -e
 HERE="$(cd "$(dirname "$0")" && pwd)"
 OUT="$HERE/../etainv/lib"
-OBJ="$HERE/obj"; LIBNAME=libetainv_hip.so; SRCS="step_kernels regularize proximal igemm norm attention misc maps aux_nets f32path ppgemm ppconv"
+OBJ="$HERE/obj"; LIBNAME=libetainv_hip.so; SRCS="step_kernels regularize proximal metrics igemm norm attention misc maps aux_nets f32path ppgemm ppconv"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result"
 mkdir -p "$OUT" "$OBJ"
 pids=()
@@ -29,8 +29,9 @@ echo "built $OUT/$LIBNAME"
 # two.  RESOURCES=1 prints what this compiler gives (the lines to compare are "VGPRs:", "VGPRs Spill:", "ScratchSize").
 # proximal.hip keeps up to 32 values per thread in registers through five passes.  Expected, prox_guidance_kernel<Q> at 1024 threads:
 # <4> 46 VGPRs, <32> 110 VGPRs, <0> 42 VGPRs; no spill and no scratch in any of the three; 17,424 B of LDS each.
+# metrics.hip: metrics_level_kernel<float / double> at 256 threads: 114 VGPRs, no scratch, 44,456 B of LDS (three blocks per CU).
 if [ "${RESOURCES:-0}" = "1" ]; then
-  for f in regularize proximal; do
+  for f in regularize proximal metrics; do
     hipcc $FLAGS --cuda-device-only -Rpass-analysis=kernel-resource-usage -c "$HERE/$f.hip" -o /dev/null 2>&1 | grep -E "Function Name|VGPRs|ScratchSize" || true
   done
 fi

@@ -188,6 +188,11 @@ int launch_prox_guidance(const float* eps_u, const float* eps_c, float g, int mo
                          float* eps_out, const float* x, float a_from, float a_to, float* x_out, float* thr_out, int n_groups, int rows_per_group,
                          int l, hipStream_t s);
 
+// ---- metrics.hip
+// etainv_image_metrics (include/etainv.h) behind its stream cast: every refusal is made here, before anything touches the device
+int launch_image_metrics(const float* pred, const float* target, int b, int h, int w, float lo, float hi, int mask, float* out, void* workspace,
+                         int64_t workspace_bytes, hipStream_t s);
+
 // ---- maps.hip
 int launch_word_maps(const float* maps_acc, int n_layers, int n_img_cap, int rows_per_img, int row_sel, int heads, int res, int L,
                      int n_img, const int32_t* tokens, int n_tok, int steps_done, float* out, int accumulate, float scale,

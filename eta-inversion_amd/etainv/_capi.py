@@ -44,6 +44,8 @@ SIGNATURES = {
     "etainv_edict_couple_mix": [_p, _p, _i, _p, _p, _f, _f, _f, _f, _i64, _i, _p],
     "etainv_noise_regularize": [_p, _p, _f, _p, _p, _f, _f, _p, _i, _i, _p, _i, _i, _f, _f, _p],
     "etainv_prox_guidance": [_p, _p, _f, _i, _i, _i, _f, _f, _p, _p, _f, _f, _p, _p, _i, _i, _i, _p],
+    "etainv_image_metrics_workspace_bytes": [_i, _i, _i, _i],
+    "etainv_image_metrics": [_p, _p, _i, _i, _i, _f, _f, _i, _p, _p, _i64, _p],
     "etainv_engine_create": [C.POINTER(EngineConfig), C.POINTER(_p)],
     "etainv_engine_destroy": [_p],
     "etainv_engine_num_weights": [_p],
@@ -105,7 +107,7 @@ SIGNATURES = {
     "etainv_op_gemm_per_image": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "etainv_op_rows_broadcast": [_p, _i, _i, _i64, _i, _p],
 }
-_RESTYPES = {"etainv_last_error": C.c_char_p, "etainv_engine_workspace_bytes": _i64, "etainv_engine_weight_bytes": _i64}
+_RESTYPES = {"etainv_last_error": C.c_char_p, "etainv_engine_workspace_bytes": _i64, "etainv_image_metrics_workspace_bytes": _i64, "etainv_engine_weight_bytes": _i64}
 
 _lib = None
 

@@ -1,0 +1,9 @@
+"""Image metrics of saved edits (reference metrics/): `EditMetric` over the metric classes, and `image_metrics`, the batched call they sit on."""
+from .base import BaseMetric, SimpleMetric
+from .edit_metric import EditMetric
+from .functional import NAMES, image_metrics
+from .metrics import MSEMetric, PSNRMetric
+from .msssim import MSSSIM
+from .ssim import SSIM
+
+__all__ = ["BaseMetric", "SimpleMetric", "EditMetric", "MSEMetric", "PSNRMetric", "SSIM", "MSSSIM", "image_metrics", "NAMES"]

@@ -137,6 +137,30 @@ int etainv_prox_guidance(const float* eps_u, const float* eps_c, float g, int mo
                          float* eps_out, const float* x, float a_from, float a_to, float* x_out, float* thr_out, int n_groups,
                          int rows_per_group, int l, void* stream);
 
+/* ---- image metrics of saved edits (reference metrics/, compute_metrics.py)
+ * The four metrics of EditMetric that need no pretrained network, for b independent pairs in one call: MSEMetric (metrics/metrics.py:7-17),
+ * PSNRMetric (:23-34), MSSSIM (metrics/msssim.py:61-106, :168-247 with data_range 1) and SSIM (metrics/ssim.py:8-30, which is
+ * torchmetrics.image.StructuralSimilarityIndexMeasure() with its defaults [3P]: restated from its documented behaviour, not run here).
+ * pred, target: fp32 [b][3][h][w] in the range (lo, hi); x' = (x - lo) / (hi - lo) is applied inside the kernels.  out: fp32 [b][4] =
+ * (mse, psnr, ssim, msssim) per pair; mask picks the metrics (1 mse, 2 psnr, 4 ssim, 8 msssim), the others' slots receive NaN.
+ *   mse    mean of (pred' - target')^2 over the 3 h w elements;  psnr = 10 log10(1 / mse), +inf for identical images
+ *   window 11 taps, exp(-(i - 5)^2 / (2 * 1.5^2)) normalised, built in float32; applied along H, then along W, without padding.  With
+ *          mu = E[.], sigma = E[..] - mu mu under that window:  cs = (2 sigma12 + C2) / (sigma11 + sigma22 + C2),
+ *          ssim = (2 mu1 mu2 + C1) / (mu1^2 + mu2^2 + C1) * cs,  C1 = (0.01 R)^2, C2 = (0.03 R)^2
+ *   msssim R = 1; five levels, between them a 2 x 2 average pool with padding size % 2 whose zeros count in the divisor; per channel the mean
+ *          of cs (levels 0-3) and of ssim (level 4), each clamped at 0, raised to 0.0448, 0.2856, 0.3001, 0.2363, 0.1333 and multiplied; the
+ *          mean over the channels.  Needs min(h, w) > 160.
+ *   ssim   R = max(max pred' - min pred', max target' - min target') of the pair (torchmetrics' data_range=None); reflect padding by 5 and
+ *          cropping 5 again is the unpadded window; the mean over all channels and window positions, no clamp.  Needs h, w >= 11.  R = 0 (two
+ *          constant images, where torchmetrics divides 0 by 0): the structure term is 1, C1 = 0, and 0 / 0 is 1.
+ * Arithmetic is float64 from the normalisation on, rounded to fp32 at the end; sums run in a fixed order without atomics: a pair's results do
+ * not depend on b, on its position or on mask, and are bit-identical from run to run.  workspace: a device buffer of at least
+ * etainv_image_metrics_workspace_bytes(b, h, w, mask) bytes (-1: refused, see etainv_last_error), 8-byte aligned; its contents mean nothing
+ * between calls.  b <= 21845, h, w <= 16384. */
+int64_t etainv_image_metrics_workspace_bytes(int b, int h, int w, int mask);
+int etainv_image_metrics(const float* pred, const float* target, int b, int h, int w, float lo, float hi, int mask, float* out,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------- engine */
 typedef struct etainv_engine etainv_engine_t;
 
