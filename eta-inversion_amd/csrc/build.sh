@@ -19,8 +19,10 @@ for f in $SRCS; do
 done
 hipcc $FLAGS -x hip -c "$HERE/engine.cpp" -o "$OBJ/engine.o" &
 pids+=($!)
+hipcc $FLAGS -x hip -c "$HERE/ops_capi.cpp" -o "$OBJ/ops_capi.o" &
+pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
-objs=""; for f in $SRCS engine; do objs="$objs $OBJ/$f.o"; done
+objs=""; for f in $SRCS engine ops_capi; do objs="$objs $OBJ/$f.o"; done
 hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/$LIBNAME" $objs
 echo "built $OUT/$LIBNAME"
 # regularize.hip steers its register allocation (opaque copies of the thread index, scheduling fences every four slots: DESIGN 4.9b), which a
@@ -50,7 +52,7 @@ if [ -n "${VARIANT:-}" ]; then
   if [ "$vf" = "attention" ]; then EXTRA="-mllvm -amdgpu-mfma-vgpr-form -fno-honor-nans"; fi
   hipcc $FLAGS $EXTRA ${VARIANT_FLAGS:-} -c "$HERE/$vf.hip" -o "$OBJ/${vf}_$VARIANT.o"
   objs=""
-  for f in $SRCS engine; do
+  for f in $SRCS engine ops_capi; do
     if [ "$f" = "$vf" ]; then objs="$objs $OBJ/${vf}_$VARIANT.o"; else objs="$objs $OBJ/$f.o"; fi
   done
   hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libetainv_hip_$VARIANT.so" $objs

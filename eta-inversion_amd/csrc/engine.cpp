@@ -1,4 +1,5 @@
-// UNet executor + C ABI of libetainv_hip.so.
+// UNet executor + C ABI of libetainv_hip.so: the model, the workspace, the forward, the attention-map store and the event profiler (the per-op
+// entry points etainv_op_* of the parity tests: ops_capi.cpp).
 //
 // The engine owns: (1) the SD1.x UNet weights, re-laid-out for the kernels (conv [O][tap][I], fused QKV / KV,
 // GEGLU row-interleave, one concatenated time-embedding projection), (2) a preallocated NHWC activation
@@ -46,8 +47,6 @@ void prof_begin(int cls, double work, hipStream_t s, double bytes) {
 }
 void prof_end(hipStream_t s) { (void)hipEventRecord(g_prof.back().b, s); }
 
-enum PackMode { PK_PLAIN = 0, PK_CONV = 1, PK_GEGLU = 2, PK_CONV_IN_GEMM = 5 };   // (3 and 4 were the direct conv_in / conv_out kernels' layouts: retired)
-
 struct WeightSlot {
   std::string name;
   int64_t shape[4] = {0, 0, 0, 0};
@@ -59,7 +58,6 @@ struct WeightSlot {
   float scale = 1.0f;          // constant folded into the values in fp32 before the rounding to the compute dtype
   void** dst4 = nullptr;       // upsampler convs: also packed as four 2x2 phase kernels (launch_pack_ups4) into *dst4
   float* stage = nullptr;      // fp32 copy kept instead of packing at once: the consumer of a folded LayerNorm is packed when gamma / beta are known
-  bool stage_and_pack = false; // fp32 copy kept AND packed (proj_in: the per-image GroupNorm fold needs the fp32 values on every call)
   bool set = false;
   int64_t numel() const {
     int64_t n = 1;
@@ -83,7 +81,7 @@ struct TBlock {
   Lin proj_in, qkv, out1, q, kv, out2, ff1, ff2, proj_out;
   // LayerNorm folded into its consumer (norm1 -> fused QKV, norm2 -> attn2.to_q, norm3 -> GEGLU projection): fp32 staging copies of the
   // consumer weights, the row sums s of the packed gamma-scaled operand and c = beta W^T + bias (kernels.h, launch_ln_fold)
-  float *st_qkv = nullptr, *st_q = nullptr, *st_ff1 = nullptr, *st_pin = nullptr;   // st_pin: proj_in, for the per-image GroupNorm fold
+  float *st_qkv = nullptr, *st_q = nullptr, *st_ff1 = nullptr;
   float *s_qkv = nullptr, *c_qkv = nullptr, *s_q = nullptr, *c_q = nullptr, *s_ff1 = nullptr, *c_ff1 = nullptr;
   float q_scale = 1.0f;
 };
@@ -141,33 +139,14 @@ struct etainv_engine {
   void* gn_bufs[16] = {};
   float* gn_part[16] = {};
   float* gn_final = nullptr;
-  void* gn_wb = nullptr;
-  float* gn_cb = nullptr;
   bool gn_fused = true;
-  // ... and, opt-in (ETAINV_GN_FOLD=1), the transformer's GroupNorm (no activation) folded into proj_in through per-image weights: -1.3 % of a
-  // 128-row UNet call, nothing measurable on the whole benchmark step -- off by default
-  bool gn_fold = false;
   bool ln_fused = true;
   bool ln_folded = false;   // the gamma-scaled consumer weights are packed (redone after any set_weight)
   std::vector<hipStream_t> upload_streams;   // streams weights were uploaded on since the last fold (the fold waits for each that is not the forward's)
   uint64_t ctx_gen = 0, ctx_gen_cached = 0;  // caller's generation of the context buffer (etainv_engine_context_generation)
 
-  // ---- hipGraph replay of small UNet calls (batch 1: ~330 dependent launches of 5 - 30 us).  OPT-IN: the GPU, not the host, paces these calls -- the
-  // gap between two dependent kernels (~1.5 us) is the same inside a replayed graph as between eager launches (MI355X_MICROARCH.md, "boundary" row),
-  // and the measurement agrees: BASELINE config 2 runs 1.456 images/s with replays and 1.458 without (profiles/r04_cfg2_graph_ab.json).  One captured graph
-  // per call signature (rows, latents, io dtype, shared prefix, K / V reuse, attention-control flags); everything that changes from call to call
-  // sits behind a FIXED device address: latent / context / output staged through engine-owned buffers, the timesteps in a device vector that a
-  // by-value kernel fills in front of the replay.  Calls whose attention control carries per-step device tables (prompt-to-prompt edits) run
-  // eagerly, as do calls above ETAINV_GRAPH_MAX_ROWS rows (launch overhead is hidden there) and everything while the event profiler is on.
-  void *g_lat = nullptr, *g_ctx = nullptr, *g_out = nullptr;
-  float* g_t = nullptr;
-  struct GraphEntry { int calls = 0; bool failed = false; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; };
-  std::unordered_map<std::string, GraphEntry> graphs;
-  hipStream_t cap_stream = nullptr;   // capture happens on a stream of the engine's own (the caller's is usually the legacy default stream, which cannot capture)
   long long qkv_hm_launches = 0;      // fused QKV projections that wrote the head-major layout since creation
   bool qkv_hm = true;                 // fused QKV projections write head-major planes where the GEMM and the attention kernel both can (ETAINV_QKV_HM)
-  int graph_max_rows = 0;             // OFF by default: measured on MI355X at batch 1 (config 2) a replay is exactly as fast as the eager launches (1.456 vs 1.458 images/s)
-  int64_t graph_replays = 0, graph_captures = 0;
 };
 
 namespace {
@@ -210,9 +189,8 @@ struct Builder {
     });
   }
   // the slot keeps an fp32 copy at *holder + off (elements) instead of being packed by set_weight
-  void stage_slot(const std::string& name, float** holder, size_t off, bool and_pack = false) {
+  void stage_slot(const std::string& name, float** holder, size_t off) {
     const int idx = e->slot_by_name.at(name);
-    e->slots[idx].stage_and_pack = and_pack;
     etainv_engine* eng = e;
     fixups.push_back([eng, idx, holder, off](char*) { eng->slots[idx].stage = *holder + off; });
   }
@@ -312,10 +290,6 @@ struct Builder {
     linear(tp + ".ff.net.0.proj", t.ff1, 8 * c, c, true, PK_GEGLU);
     linear(tp + ".ff.net.2", t.ff2, c, 4 * c, true);
     conv1x1(prefix + ".proj_out", t.proj_out, c, c);
-    if (e->gn_fold && c <= 640) {
-      want(&t.st_pin, (size_t)c * c * 4);
-      stage_slot(prefix + ".proj_in.weight", &t.st_pin, 0, /*and_pack=*/true);
-    }
     if (e->ln_fused) {
       const size_t cc = (size_t)c * c;
       want(&t.st_qkv, 3 * cc * 4);
@@ -438,15 +412,9 @@ int build_workspace(etainv_engine* e) {
   for (int i = 0; i < 3; ++i) want(reinterpret_cast<void**>(&e->gn_part[12 + i]), B * hw[0] * 640 / 16 * 4);
   want(reinterpret_cast<void**>(&e->gn_part[15]), B * hmax / 16 * 4);
   want(reinterpret_cast<void**>(&e->gn_final), B * (etainv_engine::kGroups * 2 + 2 * 2560) * 4);   // (mean, rstd) + scale / shift planes
-  want(&e->gn_wb, B * 640 * 640 * 2);                                   // per-image proj_in weights of a folded GroupNorm (C <= 640)
-  want(reinterpret_cast<void**>(&e->gn_cb), B * 640 * 4);
   const size_t res = L / 4;
   e->maps_bytes = (size_t)5 * e->max_img * 2 * etainv_engine::kHeads * res * res * 77 * 4;
   want(reinterpret_cast<void**>(&e->maps_acc), e->maps_bytes);
-  want(&e->g_lat, B * 4 * L * L * 4);                                   // graph staging (fp32-sized: the boundary dtype may be fp32)
-  want(&e->g_out, B * 4 * L * L * 4);
-  want(&e->g_ctx, B * 77 * 768 * 4);
-  want(reinterpret_cast<void**>(&e->g_t), B * 4);
   e->wsbytes = plan.off;
   ETAINV_HIP(hipMalloc(reinterpret_cast<void**>(&e->wsarena), e->wsbytes));
   for (auto& f : fix) f(e->wsarena);
@@ -478,7 +446,7 @@ struct Fwd {
   }
   // launch + bookkeeping: gn_out asks the epilogue for the GroupNorm partials of p.out (when the launch shape can: launch_igemm reports the rows
   // per block, 0 otherwise)
-  int run(IGemmParams& p, bool gn_out) {
+  int run(IGemmParams p, bool gn_out = false) {
     const int idx = part_of(p.out);
     int wm = 0;
     if (gn_out && e->gn_fused && idx >= 0) {
@@ -491,7 +459,7 @@ struct Fwd {
     if (idx >= 0) part_wm[idx] = wm;
     return 0;
   }
-  // Context-independent prefix (see unet_body): a tensor computed for the first `half` batch rows is copied to rows half .. 2 half - 1, together
+  // Context-independent prefix (see etainv_unet_forward): a tensor computed for the first `half` batch rows is copied to rows half .. 2 half - 1, together
   // with the GroupNorm partials its producer left (row blocks are batch-row major: the first half is a prefix of the buffer)
   int dup_rows(void* buf, int have, int n, int hw, int c) {   // rows [0, n) -> rows [have, have + n); a batch row holds hw pixels of c channels
     const size_t elems_per_row = (size_t)hw * c;
@@ -516,111 +484,73 @@ struct Fwd {
                                   etainv_engine::kGroups, eps, silu, e->gn_final, e->dt, s);
     return launch_groupnorm(x1, x2, c1, c2, nm.g, nm.b, e->gnbuf, rows, hw, etainv_engine::kGroups, eps, silu, e->gn_scratch, e->dt, s);
   }
-  struct LnIn { const float* s; const float* c; };   // folded LayerNorm of the input rows ((mean, rstd) per row in e->lnfinal)
-  // ln_out: this GEMM writes the input of a LayerNorm -- leave (mean, rstd) of its output rows in e->lnfinal (partials from the epilogue when
-  // the launch can, combined by a small pass; else a pass over the output)
-  IGemmParams gemm_params(const void* a, const Lin& l, void* out, int M, const LnIn* ln) {   // plain LayerNorm-consumer GEMM (what gemm() builds for it)
-    IGemmParams p;
-    p.a1 = a;
-    p.w = l.w;
-    p.out = out;
-    p.M = M;
-    p.N = l.n;
-    p.c1 = l.k;
-    p.H = 1;
-    p.W = M;
-    p.Ho = 1;
-    p.Wo = M;
-    p.taps = 1;
-    p.rows_per_batch = M;
-    p.bias = ln->c;
+  // a Linear / 1x1 conv of the model on M rows; what is special to a launch is assigned by name on the result
+  static IGemmParams linear(const void* a, const Lin& l, void* out, int M) { return igemm_linear(a, l.w, l.b, out, M, l.n, l.k); }
+  // out = l(LayerNorm(x)), x [M][l.k]: the norm folded into the GEMM (s_vec / c_vec of launch_ln_fold, (mean, rstd) per row in e->lnfinal), or
+  // the standalone pass through e->lnbuf in front of it
+  int ln_consumer(IGemmParams& p, const void* x, const Norm& nm, const float* s_vec, const float* c_vec, const Lin& l, void* out, int M) {
+    if (!e->ln_fused) {
+      p = linear(e->lnbuf, l, out, M);
+      return launch_layernorm(x, nm.g, nm.b, e->lnbuf, M, l.k, 1e-5f, e->dt, s);
+    }
+    p = linear(x, l, out, M);
+    p.bias = c_vec;
     p.ln_stat = e->lnfinal;
-    p.ln_s = ln->s;
-    return p;
+    p.ln_s = s_vec;
+    return 0;
   }
-  int gemm(const void* a, const Lin& l, void* out, int M, const void* residual = nullptr, int geglu = 0, const void* a2 = nullptr,
-           int c1 = 0, int c2 = 0, bool ln_out = false, const LnIn* ln = nullptr, bool gn_out = false, int rows_per_image = 0) {
-    IGemmParams p;
-    p.a1 = a;
-    p.a2 = a2;
-    p.w = l.w;
-    p.bias = l.b;
-    p.residual = residual;
-    p.out = out;
-    p.M = M;
-    p.N = l.n;
-    p.c1 = a2 ? c1 : l.k;
-    p.c2 = a2 ? c2 : 0;
-    p.H = 1;
-    p.W = M;
-    p.Ho = 1;
-    p.Wo = M;
-    p.taps = 1;
-    p.geglu = geglu;
-    p.rows_per_batch = M;
-    if (rows_per_image) {   // per-image weights [image][n][k] and bias [image][n]
-      p.rows_per_batch = rows_per_image;
-      p.w_batch_stride = (int64_t)l.n * l.k;
-      p.bias_batch_stride = l.n;
-    }
-    if (ln) {
-      p.bias = ln->c;
-      p.ln_stat = e->lnfinal;
-      p.ln_s = ln->s;
-    }
-    if (!ln_out) return run(p, gn_out);
+  // this GEMM writes the input of a LayerNorm: when the norm is folded into its consumer, leave (mean, rstd) of the output rows in e->lnfinal
+  // (partials from the epilogue when the launch can, combined by a small pass; else a pass over the output)
+  int run_ln_out(IGemmParams p) {
+    if (!e->ln_fused) return run(p);
     p.stat_out = e->lnstat;
     int P = 0;
     if (launch_igemm(p, e->dt, s, &P)) return 1;
-    if (P == 0) return launch_row_stats(out, e->lnfinal, M, l.n, 1e-5f, e->dt, s);
-    return launch_ln_finalize(e->lnstat, P, l.n / P, 1e-5f, e->lnfinal, M, s);
+    if (P == 0) return launch_row_stats(p.out, e->lnfinal, p.M, p.N, 1e-5f, e->dt, s);
+    return launch_ln_finalize(e->lnstat, P, p.N / P, 1e-5f, e->lnfinal, p.M, s);
   }
-  int conv(const void* a, const Lin& l, void* out, int H, int W, int stride, int ups, const float* rowvec, const void* residual, bool gn_out = true) {
-    IGemmParams p;
-    p.a1 = a;
-    p.w = l.w;
-    p.bias = l.b;
-    p.rowvec = rowvec;
+  // conv3x3 of the model over the current rows (side x side pixels each); the time row and the residual are assigned by name on the result
+  IGemmParams conv3x3(const void* a, const Lin& l, void* out, int side, int stride, int ups) const {
+    IGemmParams p = igemm_conv3x3(a, l.w, l.b, out, rows, side, side, l.k, l.n, stride, ups);
     p.rowvec_stride = e->tproj_total;
-    p.residual = residual;
-    p.out = out;
-    p.c1 = l.k;
-    p.H = H;
-    p.W = W;
-    p.Ho = ups ? H * 2 : (stride == 2 ? H / 2 : H);
-    p.Wo = ups ? W * 2 : (stride == 2 ? W / 2 : W);
-    p.stride = stride;
-    p.ups = ups;
-    p.taps = 9;
-    p.M = rows * p.Ho * p.Wo;
-    p.N = l.n;
-    p.rows_per_batch = p.Ho * p.Wo;
-    if (ups && l.w4) {   // four 2 x 2 phase convs on the source image instead of nine taps on the upsampled one (4 / 9 of the FLOPs) where the ring can
+    return p;
+  }
+  int run_conv(const IGemmParams& p, const Lin& l) {
+    if (p.ups && l.w4) {   // four 2 x 2 phase convs on the source image instead of nine taps on the upsampled one (4 / 9 of the FLOPs) where the ring can
       IGemmParams q = p;
       q.ups = 2;
       q.taps = 4;
       q.w = l.w4;
-      if (igemm_ups4_ok(q, e->dt)) return run(q, gn_out);
+      if (igemm_ups4_ok(q, e->dt)) return run(q, true);
     }
-    return run(p, gn_out);
+    return run(p, true);
   }
   // x = cat[x1 (c1), x2 (c2)] -> out
   // pnp_site: this is up_blocks[1].resnets[1], the one block of the plug-and-play feature injection
   int resblock(const ResBlock& r, const void* x1, const void* x2, int c1, int c2, int side, void* out, bool pnp_site = false) {
     const int hw = side * side;
     if (groupnorm(x1, x2, c1, c2, r.n1, hw, 1e-5f, 1)) return 1;
-    if (conv(e->gnbuf, r.conv1, e->h1, side, side, 1, 0, e->tprojbuf + r.tproj_off, nullptr)) return 1;
+    IGemmParams cv1 = conv3x3(e->gnbuf, r.conv1, e->h1, side, /*stride=*/1, /*ups=*/0);
+    cv1.rowvec = e->tprojbuf + r.tproj_off;
+    if (run_conv(cv1, r.conv1)) return 1;
     if (groupnorm(e->h1, nullptr, r.cout, 0, r.n2, hw, 1e-5f, 1)) return 1;
     // plug-and-play: conv2's output of the target rows is that of the u_s row of their image (pnp_utils.py conv_forward) -- conv2 is a function of its
     // input row alone, so the substitution happens on its input; the shortcut / residual term below stays each row's own
     if (pnp_site && ctrl && ctrl->mode == ETAINV_ATTN_PNP && ctrl->pnp_conv_active &&
         launch_rows_broadcast(e->gnbuf, rows, ctrl->n_img, (int64_t)hw * r.cout, e->dt, s)) return 1;
-    const void* residual = x1;
+    IGemmParams cv2 = conv3x3(e->gnbuf, r.conv2, out, side, /*stride=*/1, /*ups=*/0);
+    cv2.residual = x1;
     if (r.shortcut.w) {
-      if (gemm(x1, r.shortcut, e->scbuf, rows * hw, nullptr, 0, x2, c1, c2)) return 1;
-      residual = e->scbuf;
+      IGemmParams sc = linear(x1, r.shortcut, e->scbuf, rows * hw);
+      if (x2) {
+        sc.a2 = x2;
+        sc.c1 = c1;
+        sc.c2 = c2;
+      }
+      if (run(sc)) return 1;
+      cv2.residual = e->scbuf;
     }
-    return conv(e->gnbuf, r.conv2, out, side, side, 1, 0, nullptr, residual);
+    return run_conv(cv2, r.conv2);
   }
   // self_rows (0 = all): the sublayers in front of the cross-attention (GroupNorm, proj_in, QKV, self-attention, to_out + residual) do not see
   // the text context; when batch rows r and r + self_rows carry the same latent and timestep (the uncond / cond halves of a CFG call) they are
@@ -637,49 +567,32 @@ struct Fwd {
       if (ctrl->mode == ETAINV_ATTN_PNP && ctrl->pnp_qk_active && blk >= 8) mode = 3;   // up_blocks[1].attentions[1] onwards (pnp.py register_pnp)
     }
     const int all_rows = rows;
-    if (self_rows <= 0 || self_rows >= all_rows || 2 * self_rows < all_rows || mode != 0 || e->gn_fold) self_rows = all_rows;   // (a row remap couples the halves: no sharing)
+    if (self_rows <= 0 || self_rows >= all_rows || 2 * self_rows < all_rows || mode != 0) self_rows = all_rows;   // (a row remap couples the halves: no sharing)
     rows = self_rows;
     int M = rows * hw;
-    // The GroupNorm in front of proj_in has no activation: with its statistics known from the producer's epilogue it becomes a per-image scaling
-    // of proj_in's input channels + a per-image bias -- folded into per-image copies of the (small) weight matrix instead of a pass over x.
-    // Levels with C <= 640 (C = 1280: the 128 weight copies would cost more than the pass) and images that are whole M tiles.
-    const int ix = part_of(x), wx = ix >= 0 ? part_wm[ix] : 0;
-    if (e->gn_fold && t.st_pin && wx > 0 && hw % wx == 0 && hw % 256 == 0) {
-      if (launch_gn_finalize(c, 0, e->gn_part[ix], wx, nullptr, 0, rows, hw, etainv_engine::kGroups, 1e-6f, e->gn_final, s)) return 1;
-      if (launch_gn_fold(t.st_pin, t.gn.g, t.gn.b, t.proj_in.b, e->gn_final, etainv_engine::kGroups, rows, c, c, e->gn_wb, e->gn_cb, e->dt, s)) return 1;
-      Lin pin;
-      pin.w = e->gn_wb;
-      pin.b = e->gn_cb;
-      pin.n = c;
-      pin.k = c;
-      if (gemm(x, pin, e->hsA, M, nullptr, 0, nullptr, 0, 0, fold, nullptr, false, hw)) return 1;
-    } else {
-      if (groupnorm(x, nullptr, c, 0, t.gn, hw, 1e-6f, 0)) return 1;
-      if (gemm(e->gnbuf, t.proj_in, e->hsA, M, nullptr, 0, nullptr, 0, 0, fold)) return 1;
-    }
+    if (groupnorm(x, nullptr, c, 0, t.gn, hw, 1e-6f, 0)) return 1;
+    if (run_ln_out(linear(e->gnbuf, t.proj_in, e->hsA, M))) return 1;
     // self-attention
     int head_major = 0;   // the fused QKV projection writes head-major planes when both sides can (section 4.2: a 64-key tile becomes one contiguous block)
-    if (fold) {
-      const LnIn ln1{t.s_qkv, t.c_qkv};
-      if (e->qkv_hm && self_attn_prescaled_hm_ok(d, e->dt)) {
-        IGemmParams q = gemm_params(e->hsA, t.qkv, e->qkvbuf, M, &ln1);
-        q.hm_heads = etainv_engine::kHeads;
-        q.hm_dim = d;
-        q.hm_tokens = hw;
-        if (igemm_hm_ok(q, e->dt)) {
-          head_major = 1;
-          ++e->qkv_hm_launches;
-          if (run(q, false)) return 1;
-        }
+    IGemmParams qkv;
+    if (ln_consumer(qkv, e->hsA, t.ln1, t.s_qkv, t.c_qkv, t.qkv, e->qkvbuf, M)) return 1;
+    if (fold && e->qkv_hm && self_attn_prescaled_hm_ok(d, e->dt)) {
+      IGemmParams hm = qkv;
+      hm.hm_heads = etainv_engine::kHeads;
+      hm.hm_dim = d;
+      hm.hm_tokens = hw;
+      if (igemm_hm_ok(hm, e->dt)) {
+        head_major = 1;
+        ++e->qkv_hm_launches;
+        qkv = hm;
       }
-      if (!head_major && gemm(e->hsA, t.qkv, e->qkvbuf, M, nullptr, 0, nullptr, 0, 0, false, &ln1)) return 1;
-    } else {
-      if (launch_layernorm(e->hsA, t.ln1.g, t.ln1.b, e->lnbuf, M, c, 1e-5f, e->dt, s)) return 1;
-      if (gemm(e->lnbuf, t.qkv, e->qkvbuf, M)) return 1;
     }
+    if (run(qkv)) return 1;
     if (launch_self_attention_mode(e->qkvbuf, e->attnbuf, rows, hw, etainv_engine::kHeads, d, mode, n_img, e->dt, s, /*q_prescaled=*/self_attn_prescaled_hm_ok(d, e->dt),
                                    ctrl ? (ctrl->src_exit_block ? -1 : ctrl->first_row) : 0, head_major)) return 1;
-    if (gemm(e->attnbuf, t.out1, e->hsB, M, e->hsA, 0, nullptr, 0, 0, fold)) return 1;
+    IGemmParams o1 = linear(e->attnbuf, t.out1, e->hsB, M);
+    o1.residual = e->hsA;
+    if (run_ln_out(o1)) return 1;
     if (self_rows != all_rows) {   // the other half of the batch enters the cross-attention with the same residual stream (and LayerNorm statistics)
       const size_t off = (size_t)M * c * e->esz, Mn = (size_t)(all_rows - self_rows) * hw;   // rows [0, all - self) -> rows [self, all)
       ETAINV_HIP(hipMemcpyAsync(reinterpret_cast<char*>(e->hsB) + off, e->hsB, Mn * c * e->esz, hipMemcpyDeviceToDevice, s));
@@ -688,16 +601,11 @@ struct Fwd {
       M = rows * hw;
     }
     // cross-attention
-    if (fold) {
-      const LnIn ln2{t.s_q, t.c_q};
-      if (gemm(e->hsB, t.q, e->qbuf, M, nullptr, 0, nullptr, 0, 0, false, &ln2)) return 1;
-    } else {
-      if (launch_layernorm(e->hsB, t.ln2.g, t.ln2.b, e->lnbuf, M, c, 1e-5f, e->dt, s)) return 1;
-      if (gemm(e->lnbuf, t.q, e->qbuf, M)) return 1;
-    }
+    IGemmParams q;
+    if (ln_consumer(q, e->hsB, t.ln2, t.s_q, t.c_q, t.q, e->qbuf, M) || run(q)) return 1;
     void* kvb = e->kvcache[blk];
     // (all rows of the call's context, also behind a src_exit_block: a later call that reuses the cache may exit later)
-    if (!kv_reuse && gemm(e->ctxT, t.kv, kvb, ctx_rows * etainv_engine::kCtx)) return 1;
+    if (!kv_reuse && run(linear(e->ctxT, t.kv, kvb, ctx_rows * etainv_engine::kCtx))) return 1;
     CrossParams cp;
     cp.N = hw;
     cp.heads = etainv_engine::kHeads;
@@ -718,17 +626,20 @@ struct Fwd {
       }
     }
     if (launch_cross_attention_p(e->qbuf, kvb, e->attnbuf, rows, d, cp, e->dt, s)) return 1;
-    if (gemm(e->attnbuf, t.out2, e->hsA, M, e->hsB, 0, nullptr, 0, 0, fold)) return 1;
+    IGemmParams o2 = linear(e->attnbuf, t.out2, e->hsA, M);
+    o2.residual = e->hsB;
+    if (run_ln_out(o2)) return 1;
     // feed-forward (GEGLU)
-    if (fold) {
-      const LnIn ln3{t.s_ff1, t.c_ff1};
-      if (gemm(e->hsA, t.ff1, e->ffbuf, M, nullptr, 1, nullptr, 0, 0, false, &ln3)) return 1;
-    } else {
-      if (launch_layernorm(e->hsA, t.ln3.g, t.ln3.b, e->lnbuf, M, c, 1e-5f, e->dt, s)) return 1;
-      if (gemm(e->lnbuf, t.ff1, e->ffbuf, M, nullptr, 1)) return 1;
-    }
-    if (gemm(e->ffbuf, t.ff2, e->hsB, M, e->hsA)) return 1;
-    return gemm(e->hsB, t.proj_out, out, M, x, 0, nullptr, 0, 0, false, nullptr, /*gn_out=*/true);
+    IGemmParams ff1;
+    if (ln_consumer(ff1, e->hsA, t.ln3, t.s_ff1, t.c_ff1, t.ff1, e->ffbuf, M)) return 1;
+    ff1.geglu = 1;
+    if (run(ff1)) return 1;
+    IGemmParams ff2 = linear(e->ffbuf, t.ff2, e->hsB, M);
+    ff2.residual = e->hsA;
+    if (run(ff2)) return 1;
+    IGemmParams po = linear(e->hsB, t.proj_out, out, M);
+    po.residual = x;
+    return run(po, /*gn_out=*/true);
   }
 };
 
@@ -762,9 +673,6 @@ extern "C" int etainv_engine_create(const etainv_engine_config* cfg, etainv_engi
   // fp32-operand mode: the standalone norms (the folds are fusions of the 16-bit kernels' epilogues)
   e->ln_fused = !env_on("ETAINV_LN_UNFUSED") && e->dt != ETAINV_F32;
   e->gn_fused = !env_on("ETAINV_GN_UNFUSED") && e->dt != ETAINV_F32;
-  e->gn_fold = e->gn_fused && env_on("ETAINV_GN_FOLD");
-  // hipGraph replay of small calls: opt-in, ETAINV_GRAPH_MAX_ROWS=<rows> (calls of at most that many UNet rows are captured and replayed)
-  e->graph_max_rows = env_int("ETAINV_GRAPH_MAX_ROWS", e->graph_max_rows);
   e->qkv_hm = env_flag("ETAINV_QKV_HM", true);   // (default on: +0.8 % on the benchmark step, +1 % on config 5; "0" = row-major)
   if (build_model(e) || build_workspace(e)) {
     etainv_engine_destroy(e);
@@ -776,11 +684,6 @@ extern "C" int etainv_engine_create(const etainv_engine_config* cfg, etainv_engi
 
 extern "C" int etainv_engine_destroy(etainv_engine_t* e) {
   if (!e) return 0;
-  for (auto& kv : e->graphs) {
-    if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-    if (kv.second.graph) (void)hipGraphDestroy(kv.second.graph);
-  }
-  if (e->cap_stream) (void)hipStreamDestroy(e->cap_stream);
   if (e->warena) (void)hipFree(e->warena);
   if (e->maps_alt) (void)hipFree(e->maps_alt);
   if (e->wsarena) (void)hipFree(e->wsarena);
@@ -808,8 +711,11 @@ extern "C" int etainv_engine_set_weight(etainv_engine_t* e, const char* name, co
   ETAINV_CHECK(numel == s.numel(), std::string("size mismatch for ") + name);
   int64_t rows = s.shape[0], cols = s.numel() / s.shape[0];
   if (s.ndim == 1) { rows = s.shape[0]; cols = 1; }
-  if (s.stage) ETAINV_HIP(hipMemcpyAsync(s.stage, data, (size_t)numel * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  if ((!s.stage || s.stage_and_pack) && launch_pack_weight(data, s.dst, rows, cols, s.pack, s.taps, s.dst_dtype, (hipStream_t)stream, s.scale)) return 1;
+  if (s.stage) {   // a staged slot is copied (fold_layernorms packs it), any other is packed
+    ETAINV_HIP(hipMemcpyAsync(s.stage, data, (size_t)numel * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  } else if (launch_pack_weight(data, s.dst, rows, cols, s.pack, s.taps, s.dst_dtype, (hipStream_t)stream, s.scale)) {
+    return 1;
+  }
   if (s.dst4 && launch_pack_ups4(data, *s.dst4, (int)s.shape[0], (int)s.shape[1], s.dst_dtype, (hipStream_t)stream)) return 1;
   s.set = true;
   e->ln_folded = false;
@@ -861,78 +767,6 @@ extern "C" int etainv_engine_context_generation(etainv_engine_t* e, uint64_t gen
 extern "C" int64_t etainv_engine_workspace_bytes(etainv_engine_t* e) { return e ? (int64_t)e->wsbytes : 0; }
 extern "C" int64_t etainv_engine_weight_bytes(etainv_engine_t* e) { return e ? (int64_t)e->wbytes : 0; }
 
-static int unet_body(etainv_engine_t* e, const void* latent, int n_lat, const int64_t* t_host, const void* ctx, int n_rows,
-                     const etainv_attn_ctrl* ctrl, void* out, int io_dtype, void* stream, const float* t_dev, int kv_reuse_forced);
-
-static size_t io_size(int dt) { return dt == ETAINV_F32 ? 4 : 2; }
-
-// Replay of a captured call (see etainv_engine::graphs).  Returns 0 = replayed, 1 = error (message set), 2 = not taken: run the call eagerly.
-static int unet_graph(etainv_engine_t* e, const void* latent, int n_lat, const int64_t* t_host, const void* ctx, int n_rows, const etainv_attn_ctrl* ctrl,
-                      void* out, int io_dtype, void* stream) {
-  if (e->graph_max_rows <= 0 || n_rows > e->graph_max_rows || prof_enabled()) return 2;
-  if (ctrl && (ctrl->mapper || ctrl->alphas || ctrl->replace_mat || ctrl->equalizer || ctrl->cross_alpha)) return 2;   // per-step device tables
-  hipStream_t s = (hipStream_t)stream;
-  if (e->ln_fused && !e->ln_folded && fold_layernorms(e, s)) return 1;   // (host work with stream synchronisation: never inside a capture)
-  bool t_pairs = n_rows > n_lat && n_rows <= 2 * n_lat;                   // what unet_body's shared-prefix decision reads from the timesteps
-  for (int r = n_lat; t_pairs && r < n_rows; ++r) t_pairs = t_host[r] == t_host[r - n_lat];
-  const bool reuse = e->ctx_cache_on && e->ctx_cached == ctx && e->ctx_rows == n_rows && e->ctx_io == io_dtype && e->ctx_gen_cached == e->ctx_gen;
-  std::string key;   // (built with std::to_string: no fixed buffer a long signature could truncate into another signature's key)
-  for (const int v : {n_rows, n_lat, io_dtype, (int)t_pairs, (int)reuse, e->map_div, ctrl ? ctrl->mode : -1, ctrl ? ctrl->n_img : 0, ctrl ? ctrl->store_maps : 0,
-                      ctrl ? ctrl->self_replace_active : 0, ctrl ? ctrl->self_max_tokens : 0, ctrl ? ctrl->masa_active : 0, ctrl ? ctrl->masa_first_block : 0,
-                      ctrl ? ctrl->first_row : 0, ctrl ? ctrl->src_exit_block : 0, ctrl ? ctrl->pnp_qk_active : 0, ctrl ? ctrl->pnp_conv_active : 0}) {
-    key += std::to_string(v);
-    key += '.';
-  }
-  auto& ge = e->graphs[key];
-  // the first call of a signature runs eagerly: one-time allocations, function attributes and the LayerNorm fold happen outside any capture
-  if (ge.failed || ++ge.calls < 2) return 2;
-  const size_t lat_bytes = (size_t)n_lat * 4 * e->L * e->L * io_size(io_dtype), out_bytes = (size_t)n_rows * 4 * e->L * e->L * io_size(io_dtype);
-  ETAINV_HIP(hipMemcpyAsync(e->g_lat, latent, lat_bytes, hipMemcpyDeviceToDevice, s));
-  if (!reuse) ETAINV_HIP(hipMemcpyAsync(e->g_ctx, ctx, (size_t)n_rows * etainv_engine::kCtx * etainv_engine::kCtxDim * io_size(io_dtype), hipMemcpyDeviceToDevice, s));
-  if (launch_set_timesteps(t_host, n_rows, e->g_t, s)) return 1;
-  if (!ge.exec) {
-    // (a stream that cannot be created or put into capture mode sends this signature to the eager path, like every other capture failure)
-    if ((!e->cap_stream && hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking) != hipSuccess) ||
-        hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeRelaxed) != hipSuccess) {
-      (void)hipGetLastError();
-      ge.failed = true;
-      return 2;
-    }
-    const int rc = unet_body(e, e->g_lat, n_lat, t_host, e->g_ctx, n_rows, ctrl, e->g_out, io_dtype, (void*)e->cap_stream, e->g_t, reuse ? 1 : 0);
-    hipGraph_t g = nullptr;
-    const hipError_t ec = hipStreamEndCapture(e->cap_stream, &g);
-    if (rc || ec != hipSuccess || !g || hipGraphInstantiate(&ge.exec, g, nullptr, nullptr, 0) != hipSuccess) {
-      (void)hipGetLastError();
-      if (g) (void)hipGraphDestroy(g);
-      ge.exec = nullptr;
-      ge.failed = true;                    // this signature stays on the eager path (the staged inputs are untouched copies)
-      return 2;
-    }
-    ge.graph = g;
-    ++e->graph_captures;
-  }
-  ETAINV_HIP(hipGraphLaunch(ge.exec, s));
-  ETAINV_HIP(hipMemcpyAsync(out, e->g_out, out_bytes, hipMemcpyDeviceToDevice, s));
-  ++e->graph_replays;
-  return 0;
-}
-
-extern "C" int etainv_unet_forward(etainv_engine_t* e, const void* latent, int n_lat, const int64_t* t_host, const void* ctx, int n_rows,
-                                   const etainv_attn_ctrl* ctrl, void* out, int io_dtype, void* stream) {
-  int rc = 2;
-  if (e && latent && t_host && ctx && out && n_rows >= 1 && n_rows <= e->maxB && n_lat >= 1 && n_lat <= n_rows && etainv_engine_weights_ready(e))
-    rc = unet_graph(e, latent, n_lat, t_host, ctx, n_rows, ctrl, out, io_dtype, stream);
-  if (rc == 1) return 1;
-  if (rc == 2 && unet_body(e, latent, n_lat, t_host, ctx, n_rows, ctrl, out, io_dtype, stream, nullptr, -1)) return 1;
-  if (e->ctx_cache_on) {
-    e->ctx_cached = ctx;
-    e->ctx_rows = n_rows;
-    e->ctx_io = io_dtype;
-    e->ctx_gen_cached = e->ctx_gen;
-  }
-  return 0;
-}
-
 /* fused QKV projections that wrote the head-major planes since the engine was created (tests: the layout is really on the path) */
 extern "C" int etainv_engine_qkv_head_major_count(etainv_engine_t* e, long long* launches) {
   ETAINV_CHECK(e && launches, "bad arguments");
@@ -940,15 +774,8 @@ extern "C" int etainv_engine_qkv_head_major_count(etainv_engine_t* e, long long*
   return 0;
 }
 
-extern "C" int etainv_engine_graph_stats(etainv_engine_t* e, int64_t* captures, int64_t* replays) {
-  ETAINV_CHECK(e && captures && replays, "null argument");
-  *captures = e->graph_captures;
-  *replays = e->graph_replays;
-  return 0;
-}
-
-static int unet_body(etainv_engine_t* e, const void* latent, int n_lat, const int64_t* t_host, const void* ctx, int n_rows,
-                     const etainv_attn_ctrl* ctrl, void* out, int io_dtype, void* stream, const float* t_dev, int kv_reuse_forced) {
+extern "C" int etainv_unet_forward(etainv_engine_t* e, const void* latent, int n_lat, const int64_t* t_host, const void* ctx, int n_rows,
+                                   const etainv_attn_ctrl* ctrl, void* out, int io_dtype, void* stream) {
   ETAINV_CHECK(e && latent && t_host && ctx && out, "null argument");
   ETAINV_CHECK(n_rows >= 1 && n_rows <= e->maxB, "n_rows exceeds max_unet_batch");
   ETAINV_CHECK(n_lat >= 1 && n_lat <= n_rows, "1 <= n_lat <= n_rows (UNet row r reads latent r % n_lat)");
@@ -980,31 +807,18 @@ static int unet_body(etainv_engine_t* e, const void* latent, int n_lat, const in
   f.ctx_rows = n_rows;
 
   // timesteps (by value in the kernel arguments: no host buffer outlives this call) -> embedding, MLP, all 22 projections in one GEMM
-  // (t_dev: the graph path -- the timesteps of a replay are whatever launch_set_timesteps wrote to the device vector in front of it)
-  if (t_dev ? launch_time_embedding_dev(t_dev, n_rows, etainv_engine::kCh0, e->tembuf, e->dt, s)
-            : launch_time_embedding(t_host, n_rows, etainv_engine::kCh0, e->tembuf, e->dt, s)) return 1;
-  if (f.gemm(e->tembuf, e->time1, e->temb1, n_rows)) return 1;
+  if (launch_time_embedding(t_host, n_rows, etainv_engine::kCh0, e->tembuf, e->dt, s)) return 1;
+  if (f.run(Fwd::linear(e->tembuf, e->time1, e->temb1, n_rows))) return 1;
   if (launch_silu(e->temb1, e->temb1, (int64_t)n_rows * etainv_engine::kTemb, e->dt, s)) return 1;
-  if (f.gemm(e->temb1, e->time2, e->temb2, n_rows)) return 1;
+  if (f.run(Fwd::linear(e->temb1, e->time2, e->temb2, n_rows))) return 1;
   if (launch_silu(e->temb2, e->temb2, (int64_t)n_rows * etainv_engine::kTemb, e->dt, s)) return 1;
   {
-    IGemmParams p;
-    p.a1 = e->temb2;
-    p.w = e->tproj.w;
-    p.bias = e->tproj.b;
-    p.out = e->tprojbuf;
+    IGemmParams p = Fwd::linear(e->temb2, e->tproj, e->tprojbuf, n_rows);
     p.out_f32 = 1;
-    p.M = n_rows;
-    p.N = e->tproj_total;
-    p.c1 = etainv_engine::kTemb;
-    p.W = n_rows;
-    p.Wo = n_rows;
-    p.rows_per_batch = n_rows;
     if (launch_igemm(p, e->dt, s)) return 1;
   }
-  f.kv_reuse = kv_reuse_forced >= 0 ? kv_reuse_forced != 0
-                                    : e->ctx_cache_on && e->ctx_cached == ctx && e->ctx_rows == n_rows && e->ctx_io == io_dtype && e->ctx_gen_cached == e->ctx_gen;
-  // the cache entry becomes valid only when this forward has enqueued every projection (set at the end of unet_body): an error half-way
+  f.kv_reuse = e->ctx_cache_on && e->ctx_cached == ctx && e->ctx_rows == n_rows && e->ctx_io == io_dtype && e->ctx_gen_cached == e->ctx_gen;
+  // the cache entry becomes valid only when this forward has enqueued every projection (set at the end of this function): an error half-way
   // leaves it invalid, so the next call projects again
   e->ctx_cached = nullptr;
   if (!f.kv_reuse && launch_cast_f32(ctx, io_dtype, e->ctxT, e->dt, (int64_t)n_rows * etainv_engine::kCtx * etainv_engine::kCtxDim, s)) return 1;
@@ -1017,20 +831,13 @@ static int unet_body(etainv_engine_t* e, const void* latent, int n_lat, const in
   // both halves (eta_inversion.py:320-321 `torch.cat([latent] * 2)`); the values are the same.  ETAINV_NO_PREFIX_SHARE=1: A/B switch.
   // (general form: n_lat < n_rows <= 2 n_lat -- rows r >= n_lat repeat latent r - n_lat; the 3 n_img-row backward calls of eta == 0 steps carry
   // latents [tgt, src] and rows [u_t, c_s, c_t]: the last n_img rows repeat the first n_img)
-  bool share = !env_on("ETAINV_NO_PREFIX_SHARE") && n_rows > n_lat && n_rows <= 2 * n_lat && !e->gn_fold;
+  bool share = !env_on("ETAINV_NO_PREFIX_SHARE") && n_rows > n_lat && n_rows <= 2 * n_lat;
   for (int r = n_lat; share && r < n_rows; ++r) share = t_host[r] == t_host[r - n_lat];
   const int dup_n = n_rows - n_lat;   // rows copied from the head of every shared tensor to its tail
   const int pre_rows = share ? n_lat : n_rows;
   f.rows = pre_rows;
   if (launch_im2col_in(latent, io_dtype, n_lat, pre_rows, L, e->gnbuf, e->dt, s)) return 1;
-  {
-    Lin cin_l;
-    cin_l.w = e->conv_in_w;
-    cin_l.b = e->conv_in_b;
-    cin_l.n = etainv_engine::kCh0;
-    cin_l.k = 64;
-    if (f.gemm(e->gnbuf, cin_l, e->skip[0], pre_rows * L * L, nullptr, 0, nullptr, 0, 0, false, nullptr, /*gn_out=*/true)) return 1;
-  }
+  if (f.run(igemm_linear(e->gnbuf, e->conv_in_w, e->conv_in_b, e->skip[0], pre_rows * L * L, etainv_engine::kCh0, 64), /*gn_out=*/true)) return 1;
   const int ch[4] = {320, 640, 1280, 1280};
   int ri = 0, ti = 0, si = 1, side = L;
   const void* h = e->skip[0];
@@ -1053,7 +860,7 @@ static int unet_body(etainv_engine_t* e, const void* latent, int n_lat, const in
       hc = ch[i];
     }
     if (i < 3) {
-      if (f.conv(h, e->down_conv[i], e->skip[si], side, side, 2, 0, nullptr, nullptr)) return 1;
+      if (f.run_conv(f.conv3x3(h, e->down_conv[i], e->skip[si], side, /*stride=*/2, /*ups=*/0), e->down_conv[i])) return 1;
       h = e->skip[si++];
       side /= 2;
     }
@@ -1093,29 +900,24 @@ static int unet_body(etainv_engine_t* e, const void* latent, int n_lat, const in
     }
     if (i < 3) {
       void* u = pick_tmp(e, h, nullptr);
-      if (f.conv(h, e->up_conv[i], u, side, side, 1, 1, nullptr, nullptr)) return 1;
+      if (f.run_conv(f.conv3x3(h, e->up_conv[i], u, side, /*stride=*/1, /*ups=*/1), e->up_conv[i])) return 1;
       h = u;
       side *= 2;
     }
   }
   // ---- out
   if (f.groupnorm(h, nullptr, 320, 0, e->norm_out, L * L, 1e-5f, 1)) return 1;
-  {
-    IGemmParams p;
-    p.a1 = e->gnbuf;
-    p.w = e->conv_out_w;
-    p.bias = e->conv_out_b;
-    p.out = out;
-    p.out_nchw = 4;
-    p.out_io_dtype = io_dtype;
-    p.c1 = 320;
-    p.H = p.W = p.Ho = p.Wo = L;
-    p.taps = 9;
-    p.M = f.rows * L * L;
-    p.N = 4;
-    p.rows_per_batch = L * L;
-    return launch_igemm(p, e->dt, s);
+  IGemmParams p = igemm_conv3x3(e->gnbuf, e->conv_out_w, e->conv_out_b, out, f.rows, L, L, 320, 4, /*stride=*/1, /*ups=*/0);
+  p.out_nchw = 4;
+  p.out_io_dtype = io_dtype;
+  if (launch_igemm(p, e->dt, s)) return 1;
+  if (e->ctx_cache_on) {
+    e->ctx_cached = ctx;
+    e->ctx_rows = n_rows;
+    e->ctx_io = io_dtype;
+    e->ctx_gen_cached = e->ctx_gen;
   }
+  return 0;
 }
 
 extern "C" int etainv_maps_reset(etainv_engine_t* e, void* stream) {
@@ -1167,15 +969,13 @@ extern "C" int etainv_maps_word_maps_ex(etainv_engine_t* e, int n_img, const int
 extern "C" int etainv_maps_word_maps(etainv_engine_t* e, int n_img, const int32_t* tokens, int n_tok, int steps_done, float* out,
                                      int accumulate, float scale, void* stream) {
   ETAINV_CHECK(e && n_img >= 1 && n_img <= e->max_img, "bad arguments");
-  return launch_word_maps(e->maps_cur, e->map_layers, e->max_img, 2, 0, etainv_engine::kHeads, e->L / e->map_div, e->L, n_img, tokens, n_tok, steps_done, out,
-                          accumulate, scale, (hipStream_t)stream);
+  return etainv_maps_word_maps_ex(e, n_img, tokens, n_tok, steps_done, /*row_sel=*/0, /*layer_mask=*/~0u, out, accumulate, scale, stream);
 }
 
 extern "C" int etainv_maps_word_maps_role(etainv_engine_t* e, int n_img, const int32_t* tokens, int n_tok, int steps_done, int row_sel,
                                           float* out, int accumulate, float scale, void* stream) {
   ETAINV_CHECK(e && n_img >= 1 && n_img <= e->max_img && (row_sel == 0 || row_sel == 1), "bad arguments");
-  return launch_word_maps(e->maps_cur, e->map_layers, e->max_img, 2, row_sel, etainv_engine::kHeads, e->L / e->map_div, e->L, n_img, tokens, n_tok, steps_done, out,
-                          accumulate, scale, (hipStream_t)stream);
+  return etainv_maps_word_maps_ex(e, n_img, tokens, n_tok, steps_done, row_sel, /*layer_mask=*/~0u, out, accumulate, scale, stream);
 }
 
 extern "C" int etainv_local_blend(etainv_engine_t* e, float* x, int n_img, const float* blend_alpha, float thres, void* stream) {
@@ -1194,424 +994,63 @@ extern "C" int etainv_prof_reset(void) {
   g_prof_used = 0;
   return 0;
 }
-/* Sum of event-timed durations (ms), work (FLOPs or bytes) and launch count of one kernel class since the last reset.
- * Synchronises the device (diagnostic call, never used inside the loops). */
+// fn(record, event-timed ms) for every launch of one kernel class since the last reset, in launch order.  Synchronises the device (the readers below
+// are diagnostic calls, never used inside the loops).
+template <typename F>
+static int prof_visit(int cls, F fn) {
+  ETAINV_HIP(hipDeviceSynchronize());
+  for (const ProfRec& r : g_prof)
+    if (r.cls == cls) {
+      float ms = 0.f;
+      ETAINV_HIP(hipEventElapsedTime(&ms, r.a, r.b));
+      fn(r, ms);
+    }
+  return 0;
+}
+/* Sum of the durations (ms), work (FLOPs or bytes) and launch count of one kernel class. */
 extern "C" int etainv_prof_read(int cls, double* ms, double* work, int64_t* launches) {
   ETAINV_CHECK(cls >= 0 && cls < PROF_NCLASS && ms && work && launches, "bad arguments");
-  ETAINV_HIP(hipDeviceSynchronize());
-  double t = 0, w = 0;
-  int64_t n = 0;
-  for (auto& r : g_prof)
-    if (r.cls == cls) {
-      float f = 0.f;
-      ETAINV_HIP(hipEventElapsedTime(&f, r.a, r.b));
-      t += f;
-      w += r.work;
-      ++n;
-    }
-  *ms = t;
-  *work = w;
-  *launches = n;
-  return 0;
+  *ms = *work = 0.0;
+  *launches = 0;
+  return prof_visit(cls, [&](const ProfRec& r, float t) {
+    *ms += t;
+    *work += r.work;
+    ++*launches;
+  });
+}
+// the first `cap` launches of one class, one entry each (bytes: optional); *launches = how many there were
+static int prof_records(int cls, double* ms, double* work, double* bytes, int64_t cap, int64_t* launches) {
+  *launches = 0;
+  return prof_visit(cls, [&](const ProfRec& r, float t) {
+    const int64_t n = (*launches)++;
+    if (n >= cap) return;
+    ms[n] = t;
+    work[n] = r.work;
+    if (bytes) bytes[n] = r.bytes;
+  });
 }
 extern "C" int etainv_prof_records(int cls, double* ms, double* work, int64_t cap, int64_t* launches) {
   ETAINV_CHECK(cls >= 0 && cls < PROF_NCLASS && ms && work && launches && cap >= 0, "bad arguments");
-  ETAINV_HIP(hipDeviceSynchronize());
-  int64_t n = 0;
-  for (auto& r : g_prof)
-    if (r.cls == cls) {
-      if (n < cap) {
-        float f = 0.f;
-        ETAINV_HIP(hipEventElapsedTime(&f, r.a, r.b));
-        ms[n] = f;
-        work[n] = r.work;
-      }
-      ++n;
-    }
-  *launches = n;
-  return 0;
+  return prof_records(cls, ms, work, nullptr, cap, launches);
 }
-
 /* etainv_prof_records + the algorithmic HBM bytes of every launch (0 for classes that record none): joins a per-launch PMC traffic pass
  * (tools/pmc_per_launch.py) with what each launch had to move at minimum */
 extern "C" int etainv_prof_records_ex(int cls, double* ms, double* work, double* bytes, int64_t cap, int64_t* launches) {
   ETAINV_CHECK(cls >= 0 && cls < PROF_NCLASS && ms && work && bytes && launches && cap >= 0, "bad arguments");
-  ETAINV_HIP(hipDeviceSynchronize());
-  int64_t n = 0;
-  for (auto& r : g_prof)
-    if (r.cls == cls) {
-      if (n < cap) {
-        float f = 0.f;
-        ETAINV_HIP(hipEventElapsedTime(&f, r.a, r.b));
-        ms[n] = f;
-        work[n] = r.work;
-        bytes[n] = r.bytes;
-      }
-      ++n;
-    }
-  *launches = n;
-  return 0;
+  return prof_records(cls, ms, work, bytes, cap, launches);
 }
-
 /* Roofline split of one class: launches whose arithmetic intensity work / bytes is at least `ridge` (FLOP per byte; MFMA peak / HBM peak) are
  * MFMA-bound, the rest HBM-bound.  out[0..2] = ms, FLOPs, bytes of the MFMA-bound launches; out[3..5] = the same of the HBM-bound ones. */
 extern "C" int etainv_prof_split(int cls, double ridge, double* out6, int64_t* launches2) {
   ETAINV_CHECK(cls >= 0 && cls < PROF_NCLASS && out6 && launches2, "bad arguments");
-  ETAINV_HIP(hipDeviceSynchronize());
   for (int k = 0; k < 6; ++k) out6[k] = 0.0;
   launches2[0] = launches2[1] = 0;
-  for (auto& r : g_prof)
-    if (r.cls == cls && r.bytes > 0.0) {
-      float f = 0.f;
-      ETAINV_HIP(hipEventElapsedTime(&f, r.a, r.b));
-      const int o = (r.work / r.bytes >= ridge) ? 0 : 3;
-      out6[o] += f;
-      out6[o + 1] += r.work;
-      out6[o + 2] += r.bytes;
-      ++launches2[o / 3];
-    }
-  return 0;
-}
-
-// ---- per-op entry points for the parity tests
-extern "C" int etainv_op_gemm(const void* a, const void* w, const void* bias, const void* residual, void* out, int m, int n, int k,
-                              int geglu, int dtype, void* stream) {
-  IGemmParams p;
-  p.a1 = a;
-  p.w = w;
-  p.bias = (const float*)bias;
-  p.residual = residual;
-  p.out = out;
-  p.M = m;
-  p.N = n;
-  p.c1 = k;
-  p.W = m;
-  p.Wo = m;
-  p.geglu = geglu;
-  p.rows_per_batch = m;
-  return launch_igemm(p, dtype, (hipStream_t)stream);
-}
-
-extern "C" int etainv_op_gemm_ln(const void* a, const void* w_folded, const float* c_vec, const float* s_vec, const float* stat,
-                                 const void* residual, void* out, float* stat_out, int* stat_p_out, int m, int n, int k, int geglu,
-                                 int dtype, void* stream) {
-  IGemmParams p;
-  p.a1 = a;
-  p.w = w_folded;
-  p.bias = c_vec;
-  p.residual = residual;
-  p.out = out;
-  p.M = m;
-  p.N = n;
-  p.c1 = k;
-  p.W = m;
-  p.Wo = m;
-  p.geglu = geglu;
-  p.rows_per_batch = m;
-  if (stat) {
-    p.ln_stat = stat;
-    p.ln_s = s_vec;
-  }
-  p.stat_out = stat_out;
-  return launch_igemm(p, dtype, (hipStream_t)stream, stat_p_out);
-}
-
-// the fused QKV projection as transformer() launches it: head-major planes [q|k|v][row][head][token][head_dim] when igemm_hm_ok allows (*wrote_head_major = 1),
-// the row-major LayerNorm-consumer GEMM of etainv_op_gemm_ln otherwise (0)
-extern "C" int etainv_op_gemm_ln_hm(const void* a, const void* w_folded, const float* c_vec, const float* s_vec, const float* stat, void* out, int m, int n,
-                                    int k, int heads, int head_dim, int tokens, int* wrote_head_major, int dtype, void* stream) {
-  ETAINV_CHECK(stat && s_vec && c_vec && wrote_head_major, "the LayerNorm-consumer GEMM needs stat, s_vec, c_vec and wrote_head_major");
-  IGemmParams p;
-  p.a1 = a;
-  p.w = w_folded;
-  p.bias = c_vec;
-  p.out = out;
-  p.M = m;
-  p.N = n;
-  p.c1 = k;
-  p.W = m;
-  p.Wo = m;
-  p.rows_per_batch = m;
-  p.ln_stat = stat;
-  p.ln_s = s_vec;
-  *wrote_head_major = 0;
-  if (self_attn_prescaled_hm_ok(head_dim, dtype)) {
-    IGemmParams q = p;
-    q.hm_heads = heads;
-    q.hm_dim = head_dim;
-    q.hm_tokens = tokens;
-    if (igemm_hm_ok(q, dtype)) {
-      *wrote_head_major = 1;
-      return launch_igemm(q, dtype, (hipStream_t)stream);
-    }
-  }
-  return launch_igemm(p, dtype, (hipStream_t)stream);
-}
-
-extern "C" int etainv_op_gemm_gnstat(const void* a, const void* w, const float* bias, const void* residual, void* out, float* part, int* wm_out, int m,
-                                     int n, int k, int rows_per_image, int dtype, void* stream) {
-  IGemmParams p;
-  p.a1 = a;
-  p.w = w;
-  p.bias = bias;
-  p.residual = residual;
-  p.out = out;
-  p.M = m;
-  p.N = n;
-  p.c1 = k;
-  p.W = m;
-  p.Wo = m;
-  p.rows_per_batch = rows_per_image;
-  p.stat_out = part;
-  p.stat_kind = 1;
-  return launch_igemm(p, dtype, (hipStream_t)stream, wm_out);
-}
-
-extern "C" int etainv_op_conv3x3_gnstat(const void* x_nhwc, const void* w_okkc, const float* bias, const float* rowvec, const void* residual, void* out,
-                                        float* part, int* wm_out, int b, int h, int wd, int cin, int cout, int dtype, void* stream) {
-  IGemmParams p;
-  p.a1 = x_nhwc;
-  p.w = w_okkc;
-  p.bias = bias;
-  p.rowvec = rowvec;
-  p.rowvec_stride = cout;
-  p.residual = residual;
-  p.out = out;
-  p.c1 = cin;
-  p.H = p.Ho = h;
-  p.W = p.Wo = wd;
-  p.taps = 9;
-  p.M = b * h * wd;
-  p.N = cout;
-  p.rows_per_batch = h * wd;
-  p.stat_out = part;
-  p.stat_kind = 1;
-  return launch_igemm(p, dtype, (hipStream_t)stream, wm_out);
-}
-
-extern "C" int etainv_op_groupnorm_pre(const void* x1, const void* x2, int c1, int c2, const float* part1, int wm1, const float* part2, int wm2,
-                                       const float* gamma, const float* beta, void* out, int b, int hw, int groups, float eps, int silu,
-                                       float* final_stats, int dtype, void* stream) {
-  return launch_groupnorm_pre(x1, x2, c1, c2, part1, wm1, part2, wm2, gamma, beta, out, b, hw, groups, eps, silu, final_stats, dtype,
-                              (hipStream_t)stream);
-}
-
-extern "C" int etainv_op_ln_fold(const float* w, const float* gamma, const float* beta, const float* bias, int n, int k, int geglu, float scale,
-                                 void* w_out, float* s_out, float* c_out, int dtype, void* stream) {
-  const int mode = geglu ? PK_GEGLU : PK_PLAIN;
-  // the bias goes through the same row permutation as the weight (into c_out, which the fold then reads and overwrites element by element)
-  if (bias && launch_pack_weight(bias, c_out, n, 1, mode, 1, ETAINV_F32, (hipStream_t)stream)) return 1;
-  return launch_ln_fold(w, gamma, beta, bias ? c_out : nullptr, n, k, mode, scale, w_out, s_out, c_out, dtype, (hipStream_t)stream);
-}
-
-extern "C" int etainv_op_row_stats(const void* x, float* stat, int rows, int c, float eps, int dtype, void* stream) {
-  return launch_row_stats(x, stat, rows, c, eps, dtype, (hipStream_t)stream);
-}
-
-extern "C" int etainv_op_ln_finalize(const float* partials, int p, int cw, float eps, float* stat, int rows, void* stream) {
-  return launch_ln_finalize(partials, p, cw, eps, stat, rows, (hipStream_t)stream);
-}
-
-extern "C" int etainv_op_conv3x3_ex(const void* x_nhwc, const void* w_okkc, const void* bias, const void* residual, void* out, int b, int h,
-                                    int wd, int cin, int cout, int stride, int upsample, int pad0, int out_nchw, int out_io_dtype,
-                                    int dtype, void* stream) {
-  IGemmParams p;
-  p.a1 = x_nhwc;
-  p.w = w_okkc;
-  p.bias = (const float*)bias;
-  p.residual = residual;
-  p.out = out;
-  p.c1 = cin;
-  p.H = h;
-  p.W = wd;
-  p.Ho = upsample ? h * 2 : (stride == 2 ? h / 2 : h);
-  p.Wo = upsample ? wd * 2 : (stride == 2 ? wd / 2 : wd);
-  p.stride = stride;
-  p.ups = upsample;
-  p.taps = 9;
-  p.pad0 = pad0;
-  p.out_nchw = out_nchw;
-  p.out_io_dtype = out_io_dtype;
-  p.M = b * p.Ho * p.Wo;
-  p.N = cout;
-  p.rows_per_batch = p.Ho * p.Wo;
-  return launch_igemm(p, dtype, (hipStream_t)stream);
-}
-
-extern "C" int etainv_op_pack_ups4(const float* w_oc33, void* dst, int cout, int cin, int dtype, void* stream) {
-  return launch_pack_ups4(w_oc33, dst, cout, cin, dtype, (hipStream_t)stream);
-}
-
-extern "C" int etainv_op_conv3x3_rv(const void* x_nhwc, const void* x2_nhwc, int c1, int c2, const void* w_okkc, const void* bias, const float* rowvec,
-                                    int rowvec_stride, const void* residual, void* out, int b, int h, int wd, int cout, int stride, int upsample, int taps,
-                                    int dtype, void* stream);
-// the time row as its own dense [b][cout] matrix
-extern "C" int etainv_op_conv3x3(const void* x_nhwc, const void* x2_nhwc, int c1, int c2, const void* w_okkc, const void* bias,
-                                 const float* rowvec, const void* residual, void* out, int b, int h, int wd, int cout, int stride,
-                                 int upsample, int taps, int dtype, void* stream) {
-  return etainv_op_conv3x3_rv(x_nhwc, x2_nhwc, c1, c2, w_okkc, bias, rowvec, cout, residual, out, b, h, wd, cout, stride, upsample, taps, dtype, stream);
-}
-
-extern "C" int etainv_op_groupnorm(const void* x_nhwc, const void* x2_nhwc, int c1, int c2, const float* gamma, const float* beta,
-                                   void* out, int b, int hw, int groups, float eps, int silu, float* scratch, int dtype, void* stream) {
-  return launch_groupnorm(x_nhwc, x2_nhwc, c1, c2, gamma, beta, out, b, hw, groups, eps, silu, scratch, dtype, (hipStream_t)stream);
-}
-
-extern "C" int etainv_op_layernorm(const void* x, const float* gamma, const float* beta, void* out, int rows, int c, float eps, int dtype,
-                                   void* stream) {
-  return launch_layernorm(x, gamma, beta, out, rows, c, eps, dtype, (hipStream_t)stream);
-}
-
-extern "C" int etainv_op_self_attention(const void* qkv, void* out, int b, int n, int heads, int d, int mode, int n_img, int dtype,
-                                        void* stream) {
-  return launch_self_attention_mode(qkv, out, b, n, heads, d, mode, n_img, dtype, (hipStream_t)stream);
-}
-
-// every argument of the launcher (the engine's form: q_prescaled = 1 at head_dim 40 / 80, head-major planes, the three-row layouts through first_row)
-extern "C" int etainv_op_self_attention_ex(const void* qkv, void* out, int b, int n, int heads, int d, int mode, int n_img, int q_prescaled, int first_row,
-                                           int head_major, int dtype, void* stream) {
-  return launch_self_attention_mode(qkv, out, b, n, heads, d, mode, n_img, dtype, (hipStream_t)stream, q_prescaled, first_row, head_major);
-}
-
-extern "C" int etainv_op_rows_broadcast(void* x, int rows, int n_src, int64_t row_elems, int dtype, void* stream) {
-  return launch_rows_broadcast(x, rows, n_src, row_elems, dtype, (hipStream_t)stream);
-}
-
-extern "C" int etainv_op_cross_attention(const void* q, const void* kv, void* out, int b, int n, int heads, int d, int n_ctx,
-                                         const etainv_attn_ctrl* ctrl, int map_layer, int n_img_cap, float* maps_acc, int dtype,
-                                         void* stream) {
-  CrossParams cp;
-  cp.N = n;
-  cp.heads = heads;
-  cp.n_ctx = n_ctx;
-  cp.scale_log2 = (1.0f / std::sqrt((float)d)) * 1.4426950408889634f;
-  cp.rows = b;
-  cp.n_img_cap = n_img_cap;
-  cp.maps_acc = maps_acc;
-  cross_params_from_ctrl(cp, ctrl);
-  if (cp.layout && ctrl->store_maps && map_layer >= 0) cp.map_layer = map_layer;   // (without maps_acc: the launcher's refusal, not a silent loss of maps)
-  return launch_cross_attention_p(q, kv, out, b, d, cp, dtype, (hipStream_t)stream);
-}
-
-// conv3x3 (+ second source, fused upsample, stride 2) with the time row read the way the UNet reads it: rowvec points at this layer's columns inside the
-// [b][rowvec_stride] fp32 matrix of all time projections
-extern "C" int etainv_op_conv3x3_rv(const void* x_nhwc, const void* x2_nhwc, int c1, int c2, const void* w_okkc, const void* bias,
-                                    const float* rowvec, int rowvec_stride, const void* residual, void* out, int b, int h, int wd, int cout,
-                                    int stride, int upsample, int taps, int dtype, void* stream) {
-  ETAINV_CHECK(!rowvec || rowvec_stride >= cout, "rowvec_stride must cover the cout columns of a row");
-  IGemmParams p;
-  p.a1 = x_nhwc;
-  p.a2 = x2_nhwc;
-  p.w = w_okkc;
-  p.bias = (const float*)bias;
-  p.rowvec = rowvec;
-  p.rowvec_stride = rowvec_stride;
-  p.residual = residual;
-  p.out = out;
-  p.c1 = c1;
-  p.c2 = c2;
-  p.H = h;
-  p.W = wd;
-  p.Ho = upsample ? h * 2 : (stride == 2 ? h / 2 : h);
-  p.Wo = upsample ? wd * 2 : (stride == 2 ? wd / 2 : wd);
-  p.stride = stride;
-  p.ups = upsample;
-  p.taps = taps;
-  p.M = b * p.Ho * p.Wo;
-  p.N = cout;
-  p.rows_per_batch = p.Ho * p.Wo;
-  return launch_igemm(p, dtype, (hipStream_t)stream);
-}
-
-// the GEMM of all time-embedding projections as unet_body launches it: fp32 output [m][n]
-extern "C" int etainv_op_gemm_f32out(const void* a, const void* w, const float* bias, float* out_f32, int m, int n, int k, int dtype, void* stream) {
-  IGemmParams p;
-  p.a1 = a;
-  p.w = w;
-  p.bias = bias;
-  p.out = out_f32;
-  p.out_f32 = 1;
-  p.M = m;
-  p.N = n;
-  p.c1 = k;
-  p.W = m;
-  p.Wo = m;
-  p.rows_per_batch = m;
-  return launch_igemm(p, dtype, (hipStream_t)stream);
-}
-
-extern "C" int etainv_op_gn_fold(const float* w, const float* gamma, const float* beta, const float* bias, const float* stats, int groups, int b, int n,
-                                 int k, void* wb_out, float* cb_out, int dtype, void* stream) {
-  return launch_gn_fold(w, gamma, beta, bias, stats, groups, b, n, k, wb_out, cb_out, dtype, (hipStream_t)stream);
-}
-
-// the 1x1 conv behind a folded GroupNorm as Fwd::gemm launches it: image i (hw rows) multiplies wb[i] [n][k] and adds cb[i] [n]
-extern "C" int etainv_op_gemm_per_image(const void* a, const void* wb, const float* cb, const void* residual, void* out, int b, int hw, int n, int k,
-                                        int dtype, void* stream) {
-  ETAINV_CHECK(b > 0 && hw > 0, "bad sizes");
-  IGemmParams p;
-  p.a1 = a;
-  p.w = wb;
-  p.bias = cb;
-  p.residual = residual;
-  p.out = out;
-  p.M = b * hw;
-  p.N = n;
-  p.c1 = k;
-  p.W = p.M;
-  p.Wo = p.M;
-  p.rows_per_batch = hw;
-  p.w_batch_stride = (int64_t)n * k;
-  p.bias_batch_stride = n;
-  return launch_igemm(p, dtype, (hipStream_t)stream);
-}
-
-// via_device = 0: timesteps by value in the kernel arguments; 1: through the device vector t_dev [rows] (the captured-graph route)
-extern "C" int etainv_op_time_embedding(const int64_t* t_host, int rows, int dim, void* out, int dtype, int via_device, float* t_dev, void* stream) {
-  if (!via_device) return launch_time_embedding(t_host, rows, dim, out, dtype, (hipStream_t)stream);
-  ETAINV_CHECK(t_dev, "via_device needs t_dev");
-  if (launch_set_timesteps(t_host, rows, t_dev, (hipStream_t)stream)) return 1;
-  return launch_time_embedding_dev(t_dev, rows, dim, out, dtype, (hipStream_t)stream);
-}
-
-extern "C" int etainv_op_silu(const void* x, void* out, int64_t n, int dtype, void* stream) {
-  ETAINV_CHECK(x && out && n >= 0, "null pointer or negative size");
-  if (n == 0) return 0;
-  return launch_silu(x, out, n, dtype, (hipStream_t)stream);
-}
-
-extern "C" int etainv_op_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, void* stream) {
-  ETAINV_CHECK(src && dst && n >= 0, "null pointer or negative size");
-  if (n == 0) return 0;
-  return launch_cast_f32(src, src_dtype, dst, dst_dtype, n, (hipStream_t)stream);
-}
-
-extern "C" int etainv_op_im2col_in(const void* latent, int io_dtype, int n_lat, int rows, int l, void* out, int dtype, void* stream) {
-  ETAINV_CHECK(l > 0, "bad sizes");
-  return launch_im2col_in(latent, io_dtype, n_lat, rows, l, out, dtype, (hipStream_t)stream);
-}
-
-extern "C" int etainv_op_pack_weight(const float* src, void* dst, int64_t rows, int64_t cols, int mode, int taps, float scale, const float* colscale,
-                                     int dtype, void* stream) {
-  return launch_pack_weight(src, dst, rows, cols, mode, taps, dtype, (hipStream_t)stream, scale, colscale);
-}
-
-extern "C" int etainv_op_word_maps_ex(const float* maps_acc, int n_layers, int n_img_cap, int heads, int res, int L, int n_img, const int32_t* tokens,
-                                      int n_tok, int steps_done, int row_sel, unsigned layer_mask, float* out, int accumulate, float scale, void* stream) {
-  ETAINV_CHECK(row_sel == 0 || row_sel == 1, "row_sel: 0 = source cond row, 1 = target cond row");
-  ETAINV_CHECK(n_img <= n_img_cap && heads > 0 && res > 0 && L > 0, "bad sizes");
-  return launch_word_maps(maps_acc, n_layers, n_img_cap, 2, row_sel, heads, res, L, n_img, tokens, n_tok, steps_done, out, accumulate, scale,
-                          (hipStream_t)stream, layer_mask);
-}
-
-extern "C" int etainv_op_word_maps(const float* maps_acc, int n_layers, int n_img_cap, int heads, int res, int L, int n_img,
-                                   const int32_t* tokens, int n_tok, int steps_done, float* out, int accumulate, float scale,
-                                   void* stream) {
-  return launch_word_maps(maps_acc, n_layers, n_img_cap, 2, 0, heads, res, L, n_img, tokens, n_tok, steps_done, out, accumulate, scale,
-                          (hipStream_t)stream);
-}
-
-extern "C" int etainv_op_local_blend(const float* maps_acc, int n_layers, int n_img_cap, int heads, int res, int L, float* x, int n_img,
-                                     const float* blend_alpha, float thres, void* stream) {
-  return launch_local_blend(maps_acc, n_layers, n_img_cap, heads, res, L, x, n_img, blend_alpha, thres, (hipStream_t)stream);
+  return prof_visit(cls, [&](const ProfRec& r, float t) {
+    if (r.bytes <= 0.0) return;
+    const int o = (r.work / r.bytes >= ridge) ? 0 : 3;
+    out6[o] += t;
+    out6[o + 1] += r.work;
+    out6[o + 2] += r.bytes;
+    ++launches2[o / 3];
+  });
 }

@@ -57,6 +57,44 @@ struct IGemmParams {
   const float* ln_stat = nullptr;
   const float* ln_s = nullptr;      // [N] physical column order, like bias
 };
+// The two shapes every launch starts from -- the engine's and the etainv_op_* entry points' alike; what is special to a launch (residual, geglu, second
+// source, time row, output form, statistics, head-major planes, per-image operands) is assigned by name on the result.
+// Linear / 1x1 conv: out [M][N] = a [M][K] w[N][K]^T + bias
+inline IGemmParams igemm_linear(const void* a, const void* w, const float* bias, void* out, int M, int N, int K) {
+  IGemmParams p;
+  p.a1 = a;
+  p.w = w;
+  p.bias = bias;
+  p.out = out;
+  p.M = M;
+  p.N = N;
+  p.c1 = K;
+  p.H = p.Ho = 1;
+  p.W = p.Wo = M;
+  p.taps = 1;
+  p.rows_per_batch = M;
+  return p;
+}
+// conv3x3 over NHWC [batch][H][W][cin], pad 1: stride 1 / 2, or behind a fused nearest-2x upsample (ups)
+inline IGemmParams igemm_conv3x3(const void* a, const void* w, const float* bias, void* out, int batch, int H, int W, int cin, int cout, int stride, int ups) {
+  IGemmParams p;
+  p.a1 = a;
+  p.w = w;
+  p.bias = bias;
+  p.out = out;
+  p.c1 = cin;
+  p.H = H;
+  p.W = W;
+  p.Ho = ups ? H * 2 : (stride == 2 ? H / 2 : H);
+  p.Wo = ups ? W * 2 : (stride == 2 ? W / 2 : W);
+  p.stride = stride;
+  p.ups = ups;
+  p.taps = 9;
+  p.M = batch * p.Ho * p.Wo;
+  p.N = cout;
+  p.rows_per_batch = p.Ho * p.Wo;
+  return p;
+}
 // stat_P (optional): receives the number of partials per row written to p.stat_out (0: none written)
 int launch_igemm(const IGemmParams& p, int dtype, hipStream_t s, int* stat_P = nullptr);
 bool igemm_hm_ok(const IGemmParams& p, int dtype);     // may this launch (with hm_* set) write the head-major layout?
@@ -164,12 +202,10 @@ int launch_cross_attention_p(const void* q, const void* kv, void* out, int b, in
 int launch_im2col_in(const void* latent, int io_dtype, int n_lat, int rows, int L, void* out, int dtype, hipStream_t s);
 // sinusoidal timestep embedding (flip_sin_to_cos, freq_shift 0): t_host [rows] (HOST array, passed by value in the kernel arguments) -> [rows][dim] T
 int launch_time_embedding(const int64_t* t_host, int rows, int dim, void* out, int dtype, hipStream_t s);
-// the same from DEVICE timesteps t_dev [rows] floats (written by launch_set_timesteps): replayable inside a captured hipGraph
-int launch_set_timesteps(const int64_t* t_host, int rows, float* t_dev, hipStream_t s);
-int launch_time_embedding_dev(const float* t_dev, int rows, int dim, void* out, int dtype, hipStream_t s);
 // y = silu(x) elementwise on T
 int launch_silu(const void* x, void* out, int64_t n, int dtype, hipStream_t s);
-// cast fp32 -> T with optional row permutation (weights)
+// cast fp32 -> T with optional row permutation (weights): the `mode` of launch_pack_weight / launch_ln_fold
+enum PackMode { PK_PLAIN = 0, PK_CONV = 1, PK_GEGLU = 2, PK_CONV_IN_GEMM = 5 };   // (3 and 4 were the direct conv_in / conv_out kernels' layouts: retired)
 int launch_pack_ups4(const float* src, void* dst, int cout, int cin, int dtype, hipStream_t s);   // conv3x3 weights -> four 2x2 phase kernels (IGemmParams::ups == 2)
 int launch_pack_weight(const float* src, void* dst, int64_t rows, int64_t cols, int mode, int taps, int dtype, hipStream_t s, float scale = 1.0f,
                        const float* colscale = nullptr);

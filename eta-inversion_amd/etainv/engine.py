@@ -164,13 +164,6 @@ class Engine:
         return x
 
     @property
-    def graph_stats(self):
-        """(captures, replays) of the hipGraph path of small UNet calls since the engine was created"""
-        cap, rep = C.c_int64(), C.c_int64()
-        _capi.check(self.lib.etainv_engine_graph_stats(self.h, C.byref(cap), C.byref(rep)))
-        return cap.value, rep.value
-
-    @property
     def qkv_head_major_launches(self):
         """fused QKV projections that wrote the head-major layout (ETAINV_QKV_HM=1 at engine creation) since the engine was created"""
         n = C.c_longlong()

@@ -285,12 +285,6 @@ int etainv_engine_cache_context(etainv_engine_t* e, int enable);
  * that rewrites the context tensor IN PLACE between two calls (same pointer, rows, dtype) bumps it; the built-in loops pass a fresh value per
  * loop.  The cache entry is recorded only after a forward has succeeded: an error half-way never leaves stale K / V behind. */
 int etainv_engine_context_generation(etainv_engine_t* e, uint64_t generation);
-/* hipGraph replay of small UNet calls (opt-in: ETAINV_GRAPH_MAX_ROWS=<rows>, read at engine creation; measured no faster than the eager launches
- * at batch 1 -- the dependent-kernel gap is the same inside a graph): from its
- * second occurrence on, a call signature (rows, latents, dtype, attention-control flags without per-step device tables) is captured once and replayed
- * -- latent / context / output staged through engine-owned buffers, the timesteps through a device vector.  Same results as the eager launches
- * (the replay IS those launches); captures / replays counted since engine creation. */
-int etainv_engine_graph_stats(etainv_engine_t* e, int64_t* captures, int64_t* replays);
 /* Default since round 4 (ETAINV_QKV_HM=0 at engine creation switches it off): the fused QKV projection of a transformer block writes
  * three head-major planes [q|k|v][row][head][token][head_dim] where both its GEMM kernel and the self-attention kernel can (head_dim 40 / 80, 16-bit modes,
  * whole 256-row tiles inside one batch row), so that a 64-key tile is one contiguous block.  Same values, same arithmetic: results are bit-identical.
@@ -409,9 +403,8 @@ int etainv_op_word_maps_ex(const float* maps_acc, int n_layers, int n_img_cap, i
                            const int32_t* tokens, int n_tok, int steps_done, int row_sel, unsigned layer_mask, float* out,
                            int accumulate, float scale, void* stream);
 /* The small kernels at the edges of the UNet call (tests/test_small_kernels_gpu.py).
- * etainv_op_time_embedding: sinusoidal timestep embedding [rows][dim] (flip_sin_to_cos, freq_shift 0) of the HOST timesteps t_host [rows];
- *   via_device = 0 passes them by value in the kernel arguments, 1 writes them to the device vector t_dev [rows] floats first and reads
- *   them from there (the form a captured hipGraph replays; t_dev may be NULL when via_device == 0).
+ * etainv_op_time_embedding: sinusoidal timestep embedding [rows][dim] (flip_sin_to_cos, freq_shift 0) of the HOST timesteps t_host [rows],
+ *   passed by value in the kernel arguments.
  * etainv_op_silu: out = silu(x) over n elements (out == x allowed).  etainv_op_cast: dst = (dst_dtype) src over n elements.
  * etainv_op_im2col_in: latent NCHW [n_lat][4][l][l] io_dtype -> [rows][l*l][64] dtype, k = tap * 4 + ci, columns 36..63 zero; row r reads
  *   latent r % n_lat.
@@ -419,7 +412,7 @@ int etainv_op_word_maps_ex(const float* maps_acc, int n_layers, int n_img_cap, i
  *   interleave, 5 conv_in [O][4][3][3] -> [O][64] (cols must be 36).  Modes 0, 1, 2: every element times `scale`, then (modes 0 / 2 only) times
  *   colscale[column] (may be NULL), in fp32, before the one rounding to dtype.  Mode 5 takes neither: scale must be 1 and colscale NULL.
  *   Refused: any other mode, cols % taps != 0 in mode 1, rows % 64 != 0 in mode 2. */
-int etainv_op_time_embedding(const int64_t* t_host, int rows, int dim, void* out, int dtype, int via_device, float* t_dev, void* stream);
+int etainv_op_time_embedding(const int64_t* t_host, int rows, int dim, void* out, int dtype, void* stream);
 int etainv_op_silu(const void* x, void* out, int64_t n, int dtype, void* stream);
 int etainv_op_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, void* stream);
 int etainv_op_im2col_in(const void* latent, int io_dtype, int n_lat, int rows, int l, void* out, int dtype, void* stream);

@@ -385,16 +385,12 @@ def test_local_blend_sizes_untouched_image_and_mask(capi, res, L, monkeypatch):
 HALF_ULP = {torch.float32: 2.0 ** -24, torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}
 
 
-def time_embedding(capi, t, dim, dtype, via_device):
+def time_embedding(capi, t, dim, dtype):
     rows = len(t)
     t_host = (C.c_int64 * rows)(*[int(v) for v in t])
     out = guarded_flat(rows * dim, dtype, dim)
-    t_dev = torch.full((rows + 8,), NAN, device="cuda")
-    capi.check(capi.load().etainv_op_time_embedding(t_host, rows, dim, capi.ptr(out), capi.dtype_code(dtype), via_device, capi.ptr(t_dev) if via_device else None,
-                                                    capi.stream_ptr()))
+    capi.check(capi.load().etainv_op_time_embedding(t_host, rows, dim, capi.ptr(out), capi.dtype_code(dtype), capi.stream_ptr()))
     assert_guard(out, rows * dim)
-    if via_device:
-        assert torch.equal(t_dev[:rows].cpu(), torch.tensor([float(v) for v in t])) and torch.isnan(t_dev[rows:]).all()
     return out[:rows * dim].view(rows, dim)
 
 
@@ -412,15 +408,13 @@ T_130 = ([999, 1, 3, 5, 7] + list(range(0, 1000, 8)))[::-1]      # 130 distinct 
 @pytest.mark.parametrize("t", [[0] * 5, [1] * 5, [500] * 5, [981] * 5, [999] * 5, T_130],
                          ids=["t0", "t1", "t500", "t981", "t999", "rows130"])
 def test_time_embedding(capi, dtype, t):
-    """uniform rows (one scalar in the kernel arguments) and 130 distinct timesteps (chunks of 64 rows at row0 = 0, 64, 128, the last one ragged); the
-    by-value route and the device-vector route of a captured graph give the same bits.  Bound: the fp32 argument t * freq carries at most about 4
+    """uniform rows (one scalar in the kernel arguments) and 130 distinct timesteps (chunks of 64 rows at row0 = 0, 64, 128, the last one ragged).
+    Bound: the fp32 argument t * freq carries at most about 4
     roundings of 2^-24 relative on |a| <= 999, and d cos / da <= 1: atol = 999 * 4 * 2^-24 = 2.4e-4, plus half an ulp of the output type (|value| <= 1)."""
     dim = 320
     if len(t) == 130:
         assert len(set(t)) == 130 and max(t) == 999 and min(t) == 0
-    out = time_embedding(capi, t, dim, dtype, 0)
-    out_dev = time_embedding(capi, t, dim, dtype, 1)
-    assert torch.equal(bits(out), bits(out_dev))
+    out = time_embedding(capi, t, dim, dtype)
     err = (out.cpu().double() - time_embedding_ref(t, dim)).abs()
     bound = 999 * 4 * 2.0 ** -24 + HALF_ULP[dtype]
     print(f"time embedding {dtype} rows={len(t)} t0={t[0]}: max |err| {float(err.max()):.3e} (bound {bound:.3e})")
