@@ -44,6 +44,9 @@ SIGNATURES = {
     "etainv_edict_couple_mix": [_p, _p, _i, _p, _p, _f, _f, _f, _f, _i64, _i, _p],
     "etainv_noise_regularize": [_p, _p, _f, _p, _p, _f, _f, _p, _i, _i, _p, _i, _i, _f, _f, _p],
     "etainv_prox_guidance": [_p, _p, _f, _i, _i, _i, _f, _f, _p, _p, _f, _f, _p, _p, _i, _i, _i, _p],
+    "etainv_ddpm_sample_latents": [_p, _p, _p, _i, _p, _i, _i, _i, _p],
+    "etainv_ddpm_invert_steps": [_p, _i, _i, _i, _p, _p, _f, _p, _p, _p, _p, _i, _i, _p],
+    "etainv_ddpm_backward_step": [_p, _p, _p, _p, _i, _p, _f, _f, _f, _p, _p, _i, _i, _p],
     "etainv_image_metrics_workspace_bytes": [_i, _i, _i, _i],
     "etainv_image_metrics": [_p, _p, _i, _i, _i, _f, _f, _i, _p, _p, _i64, _p],
     "etainv_engine_create": [C.POINTER(EngineConfig), C.POINTER(_p)],

@@ -90,3 +90,10 @@ def pnp_step_rows(step, n_img, conv_steps, qk_steps, source_dead):
     [u_s, u_t, c_t] per image -- the reference's PnPUnetForward cuts the cond source row -- and two, [u_t, c_t], once both injections have ended
     in a step whose source row is replayed (`source_dead`: eta(t) == 0 under skip_dead_source_rows)."""
     return (2 if source_dead and step >= max(conv_steps, qk_steps) else 3) * n_img
+
+
+def ddpm_unet_rows(S, skip, n_img, n_prompts, g_fwd=3.5):
+    """UNet sample-forwards of a DDPM inversion + backward pass (etainv.pipeline.DdpmLoop): the inversion predicts the noise of all S noised
+    latents, the uncond and the cond row of each unless the forward scale is 0 or 1; the backward pass runs the S - skip steps that are not
+    skipped, always both rows of every prompt (its guidance is one scale per prompt row)."""
+    return S * n_img * (1 if g_fwd in (0, 1) else 2) + (S - skip) * n_img * n_prompts * 2

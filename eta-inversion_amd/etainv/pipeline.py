@@ -9,6 +9,7 @@ Replaces, for B independent (source, target) pairs at once (the reference handle
   EtaInversion.diffusion_backward / predict_step_backward       reference modules/inversion/eta_inversion.py:207-294
   DiffusionInversion.sample batch layout                        reference modules/inversion/diffusion_inversion.py:462-528
   EdictInversion.predict_step_forward / predict_step_backward   reference modules/inversion/edict_inversion.py:393-420 (EdictLoop)
+  DDPMInversion.diffusion_forward / diffusion_backward          reference modules/inversion/ddpm_inversion.py:71-104,168-177 (DdpmLoop)
 """
 import functools
 import os
@@ -18,8 +19,8 @@ import torch
 
 from . import _capi
 from .engine import AttnControl
-from .flops import edict_unet_rows, exit_share
-from .plan import FULL, LAYOUTS, plan_backward
+from .flops import ddpm_unet_rows, edict_unet_rows, exit_share
+from .plan import FULL, LAYOUTS, ddpm_guided, plan_backward, plan_ddpm_chunks
 
 NUM_TRAIN = 1000
 
@@ -540,3 +541,161 @@ class EdictLoop:
     def expected_rows(self, B, n_prompts, guidance_scale_fwd=None):
         """UNet sample-forwards of one invert + one sample (flops.edict_unet_rows)"""
         return edict_unet_rows(len(self.t_fwd), len(self.t_bwd), B, n_prompts, float(guidance_scale_fwd or self.g_fwd), self.g_bwd)
+
+
+# ---------------------------------------------------------------- DDPM inversion (reference modules/inverse_schedulers/ddpm_inverse_scheduler.py, modules/inversion/ddpm_inversion.py)
+def ddpm_timesteps(S):
+    """the scheduler's S leading-spaced timesteps, descending: the index order of the noised latents `xts` (index 0 = the largest t)"""
+    return (np.arange(S) * (NUM_TRAIN // S))[::-1].astype(np.int64).copy()
+
+
+def ddpm_alpha_prev(ac, final, S, t):
+    p = int(t) - NUM_TRAIN // S
+    return float(ac[p]) if p >= 0 else float(final)
+
+
+def ddpm_variance(ac, final, S, t):
+    """get_variance (:65-84) in float64 on the fp32 table"""
+    a_t, a_p = float(ac[int(t)]), ddpm_alpha_prev(ac, final, S, t)
+    return (1 - a_p) / (1 - a_t) * (1 - a_t / a_p)
+
+
+def ddpm_sample_coefficients(ac, S, markovian, timesteps=None):
+    """float64 [S][2] = (a, b) of etainv_ddpm_sample_latents per step in draw order (ascending t): from x_0, a = sqrt(abar_t), b = sqrt(1 - abar_t)
+    (:118); Markovian, a = sqrt(abar_t / abar_prev), b = sqrt(1 - abar_t / abar_prev) with abar_prev = 1 below 0 (:121-124)"""
+    ts = ddpm_timesteps(S)[::-1] if timesteps is None else [int(t) for t in timesteps]
+    out = np.empty((len(ts), 2), dtype=np.float64)
+    for s, t in enumerate(ts):
+        p = int(t) - NUM_TRAIN // S
+        q = float(ac[int(t)]) / (float(ac[p]) if p >= 0 else 1.0) if markovian else float(ac[int(t)])
+        out[s] = q ** 0.5, (1 - q) ** 0.5
+    return out
+
+
+def ddpm_step_coefficients(ac, final, S, t):
+    """float64 [5] of etainv_ddpm_invert_steps at timestep t (:169-193 with eta = 1): sqrt(1 - abar_t), sqrt(abar_t), sqrt(abar_prev),
+    sqrt(1 - abar_prev - var), sigma = sqrt(var)"""
+    a_t, a_p, var = float(ac[int(t)]), ddpm_alpha_prev(ac, final, S, t), ddpm_variance(ac, final, S, t)
+    return np.array([(1 - a_t) ** 0.5, a_t ** 0.5, a_p ** 0.5, max(1 - a_p - var, 0.0) ** 0.5, var ** 0.5], dtype=np.float64)
+
+
+def _f32c(t, what):
+    if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+        raise ValueError(f"{what} must be a contiguous fp32 tensor, got {t.dtype}, contiguous {t.is_contiguous()}")
+    return _capi.ptr(t)
+
+
+def ddpm_sample_latents(lib, x0, noise, ab, markovian, stream=None):
+    """etainv_ddpm_sample_latents: x0 (B,4,L,L), noise (S,B,4,L,L), ab float64 [S][2] -> xts (S+1,B,4,L,L)"""
+    S, B, L = noise.shape[0], x0.shape[0], x0.shape[-1]
+    if tuple(noise.shape) != (S, B, 4, L, L) or tuple(x0.shape) != (B, 4, L, L):
+        raise ValueError(f"x0 (B,4,L,L) and noise (S,B,4,L,L) do not fit: {tuple(x0.shape)}, {tuple(noise.shape)}")
+    ab = np.ascontiguousarray(ab, dtype=np.float64)
+    assert ab.shape == (S, 2)
+    xts = torch.empty(S + 1, B, 4, L, L, dtype=torch.float32, device=x0.device)
+    _capi.check(lib.etainv_ddpm_sample_latents(_f32c(x0, "x0"), _f32c(noise, "noise"), ab.ctypes.data, int(bool(markovian)), _capi.ptr(xts), S, B, L,
+                                               stream if stream is not None else _capi.stream_ptr()))
+    return xts
+
+
+def ddpm_invert_steps(lib, xts, first, k, eps_u, eps_c, g, coef, z, x_out, eps_out, stream=None):
+    """etainv_ddpm_invert_steps on xts (S+1,B,4,L,L); eps_u (None: eps_c is the noise), eps_c, z, x_out, eps_out (None: not wanted) (k,B,4,L,L);
+    coef float64 [k][5]"""
+    S, B, L = xts.shape[0] - 1, xts.shape[1], xts.shape[-1]
+    coef = np.ascontiguousarray(coef, dtype=np.float64)
+    assert coef.shape == (k, 5)
+    for name, t in (("eps_u", eps_u), ("eps_c", eps_c), ("z", z), ("x_out", x_out), ("eps_out", eps_out)):
+        if t is not None and t.numel() != k * B * 4 * L * L:
+            raise ValueError(f"{name} must hold {k} steps of {B} latents of side {L}, got {tuple(t.shape)}")
+    _capi.check(lib.etainv_ddpm_invert_steps(_f32c(xts, "xts"), S, int(first), int(k), _f32c(eps_u, "eps_u"), _f32c(eps_c, "eps_c"), float(g),
+                                             coef.ctypes.data, _f32c(z, "z"), _f32c(x_out, "x_out"), _f32c(eps_out, "eps_out"), B, L,
+                                             stream if stream is not None else _capi.stream_ptr()))
+
+
+def ddpm_backward_step(lib, x, eps_u, eps_c, scales, z, a_t, a_p, var, out_x, out_eps, stream=None):
+    """etainv_ddpm_backward_step: x, eps_u, eps_c, out_x, out_eps (None: not wanted) (P B,4,L,L) rows [p0 x B, p1 x B, ..]; scales: P floats; z (B,4,L,L)"""
+    P, B, L = len(scales), z.shape[0], z.shape[-1]
+    for name, t in (("x", x), ("eps_u", eps_u), ("eps_c", eps_c), ("out_x", out_x), ("out_eps", out_eps)):
+        if t is not None and tuple(t.shape) != (P * B, 4, L, L):
+            raise ValueError(f"{name} must be ({P * B}, 4, {L}, {L}) = {P} prompt rows of {B} image(s), got {tuple(t.shape)}")
+    g = np.ascontiguousarray(scales, dtype=np.float32)
+    _capi.check(lib.etainv_ddpm_backward_step(_f32c(x, "x"), _f32c(eps_u, "eps_u"), _f32c(eps_c, "eps_c"), g.ctypes.data, P, _f32c(z, "z"), float(a_t),
+                                              float(a_p), float(var), _f32c(out_x, "out_x"), _f32c(out_eps, "out_eps"), B, L,
+                                              stream if stream is not None else _capi.stream_ptr()))
+
+
+class DdpmLoop:
+    """Edit-friendly DDPM inversion for B images at once.  `invert` is time-parallel: the noised latents of all steps come from one launch, so the
+    S steps' noise predictions are ceil(rows / max_unet_batch) UNet calls with one timestep per row, each followed by one
+    etainv_ddpm_invert_steps launch.  `sample` is sequential: per step one UNet call and one etainv_ddpm_backward_step launch.
+    Tensors indexed by step follow `xts`: index j belongs to timestep t_bwd[j] (index 0 = the largest t)."""
+
+    def __init__(self, engine, S=50, guidance_scale_fwd=3.5, guidance_scale_bwd=9.0, skip_steps=0.36, markovian_forward=False):
+        self.e, self.S, self.L, self.lib = engine, int(S), engine.L, engine.lib
+        self.g_fwd, self.g_bwd, self.markovian = float(guidance_scale_fwd), float(guidance_scale_bwd), bool(markovian_forward)
+        self.skip = int(skip_steps * self.S)                       # backward steps skipped (get_bwd_skip, ddpm_inversion.py:120-126); 0 skips nothing
+        ac = alphas_cumprod()
+        self.t_bwd = ddpm_timesteps(self.S)
+        self.ab = ddpm_sample_coefficients(ac, self.S, self.markovian)
+        self.coef = np.stack([ddpm_step_coefficients(ac, ac[0], self.S, t) for t in self.t_bwd])
+        self.bwd = [(float(ac[t]), ddpm_alpha_prev(ac, ac[0], self.S, t), ddpm_variance(ac, ac[0], self.S, t)) for t in self.t_bwd]
+        self.rows_executed = self.unet_calls = 0
+
+    def invert(self, z0, ctx_src, noise, guidance_scale_fwd=None):
+        """z0 (B,4,L,L) fp32; ctx_src (B,2,77,768) = [uncond, cond] per image; noise (S,B,4,L,L), the draws of sample_latents in ascending t.
+        Returns xts (S+1,B,4,L,L) and, per step in xts order, zs (the noise maps; the t = 0 one zeroed, ddpm_inversion.py:101), latents (the
+        corrected x_{t-1}) and noise_preds, each (S,B,4,L,L)."""
+        e, S, L = self.e, self.S, self.L
+        g = self.g_fwd if guidance_scale_fwd is None else float(guidance_scale_fwd)
+        guided = ddpm_guided(g)
+        B, dev = z0.shape[0], z0.device
+        xts = ddpm_sample_latents(self.lib, z0.float().contiguous(), noise.float().contiguous(), self.ab, self.markovian)
+        zs, lat, eps = (torch.empty(S, B, 4, L, L, dtype=torch.float32, device=dev) for _ in range(3))
+        ctx_u, ctx_c = ctx_src[:, 0].float(), ctx_src[:, 1].float()
+        for ch in plan_ddpm_chunks(S, e.max_unet_batch, guided, B):
+            sl = slice(ch.first, ch.first + ch.k)
+            halves = [ctx_u, ctx_c] if guided else [ctx_c if g == 1.0 else ctx_u]
+            ctx = torch.cat([h.repeat(ch.k, 1, 1) for h in halves]).contiguous()       # rows [u x k B, c x k B], a step's images side by side
+            t_rows = [int(t) for t in self.t_bwd[sl] for _ in range(B)] * len(halves)   # equal timesteps at distance k B: the halves of a step
+            out = e.unet(xts[sl].reshape(ch.k * B, 4, L, L), t_rows, ctx)
+            eps_u, eps_c = (out[:ch.k * B], out[ch.k * B:]) if guided else (None, out)
+            ddpm_invert_steps(self.lib, xts, ch.first, ch.k, eps_u, eps_c, g, self.coef[sl], zs[sl], lat[sl], eps[sl])
+            self.rows_executed += ch.rows
+            self.unet_calls += 1
+        zs[S - 1].zero_()
+        return {"xts": xts, "zs": zs, "latents": lat, "noise_preds": eps}
+
+    def sample(self, inv, ctx_list, scales=None):
+        """inv: result of `invert`; ctx_list: one (B,2,77,768) context per prompt -- [src, tgt] gives UNet rows [u_src x B, u_tgt x B, c_src x B,
+        c_tgt x B] over the latents [src x B, tgt x B].  scales: one guidance scale per prompt (default: [g_fwd, g_bwd] for two prompts, g_bwd
+        otherwise, ddpm_inversion.py:154-159).  Returns the final latents (n B, 4, L, L)."""
+        skip = self.skip
+        start = inv["latents"][skip - 1] if skip > 0 else inv["xts"][0]
+        ctx = torch.cat([torch.cat([c[:, 0] for c in ctx_list]), torch.cat([c[:, 1] for c in ctx_list])])
+        return self.backward(torch.cat([start] * len(ctx_list)), ctx, [inv["zs"][j] for j in range(skip, self.S)], scales)
+
+    def backward(self, x, ctx, zs, scales=None):
+        """the last len(zs) backward steps from x (n B,4,L,L), rows [p0 x B, p1 x B, ..], under ctx (2 n B,77,768), rows [uncond x n B, cond x n B];
+        zs: the noise map (B,4,L,L) of every step"""
+        e, L, S = self.e, self.L, self.S
+        B = zs[0].shape[0]
+        n_p = x.shape[0] // B
+        if x.shape[0] != n_p * B or ctx.shape[0] != 2 * n_p * B or len(zs) > S:
+            raise ValueError(f"{x.shape[0]} latents, {ctx.shape[0]} context rows, {B} image(s) and {len(zs)} steps of {S} do not fit")
+        if scales is None:
+            scales = [self.g_fwd, self.g_bwd] if n_p == 2 else [self.g_bwd] * n_p
+        x, ctx = x.float().contiguous().clone(), ctx.float().contiguous()
+        x_next, eps_all = torch.empty_like(x), torch.empty(2 * n_p * B, 4, L, L, dtype=torch.float32, device=x.device)
+        with e.cached_context():
+            for j, z in zip(range(S - len(zs), S), zs):
+                e.unet(x, int(self.t_bwd[j]), ctx, None, out=eps_all)
+                a_t, a_p, var = self.bwd[j]
+                ddpm_backward_step(self.lib, x, eps_all[:n_p * B], eps_all[n_p * B:], scales, z.float().contiguous(), a_t, a_p, var, x_next, None)
+                x, x_next = x_next, x
+                self.rows_executed += 2 * n_p * B
+                self.unet_calls += 1
+        return x
+
+    def expected_rows(self, B, n_prompts, guidance_scale_fwd=None):
+        """UNet sample-forwards of one invert + one sample (flops.ddpm_unet_rows)"""
+        return ddpm_unet_rows(self.S, self.skip, B, n_prompts, self.g_fwd if guidance_scale_fwd is None else float(guidance_scale_fwd))

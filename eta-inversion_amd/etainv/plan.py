@@ -51,3 +51,26 @@ def plan_backward(S, t_bwd, etas, ac, delta, L, B=1, skip_dead_source_rows=True,
                           pnp is not None and i < pnp[1], pnp is not None and i < pnp[0],
                           ptp is not None and ptp.blend_alpha is not None and (i + 1) > int(0.2 * S), cost))
     return steps
+
+
+# ---- time-parallel DDPM inversion (etainv.pipeline.DdpmLoop.invert, modules/inversion/ddpm_inversion.py): all noised latents exist before the first
+# UNet call, so the S steps go to the UNet in chunks of whole steps.  first / k: the chunk's steps, as indices into xts (index 0 = the largest t);
+# rows: its UNet rows, [u x k n_img, c x k n_img] when guided, [one half x k n_img] otherwise
+Chunk = namedtuple("Chunk", "first k rows")
+DDPM_MAX_CHUNK = 128                                    # steps per etainv_ddpm_invert_steps launch (ETAINV_DDPM_MAX_CHUNK)
+
+
+def ddpm_guided(g):
+    """predict_noise runs both halves of a step unless the scale is 0 or 1 (reference diffusion_inversion.py:263-286)"""
+    return float(g) not in (0.0, 1.0)
+
+
+def plan_ddpm_chunks(S, max_rows, guided, n_img=1):
+    """Chunks that cover the steps 0 .. S-1 once, in order, each of at most max_rows UNet rows.  The two halves of a step stay in one call."""
+    per_step = int(n_img) * (2 if guided else 1)
+    if S < 1 or n_img < 1:
+        raise ValueError(f"S and n_img must be at least 1, got {S} and {n_img}")
+    if per_step > max_rows:
+        raise ValueError(f"one step of {n_img} image(s) is {per_step} UNet rows, the engine takes {max_rows} per call")
+    k = min(max_rows // per_step, DDPM_MAX_CHUNK)
+    return [Chunk(first, min(k, S - first), min(k, S - first) * per_step) for first in range(0, S, k)]

@@ -72,8 +72,8 @@ class DiffusionInversion:
             assert fwd.timesteps[0] < fwd.timesteps[1], "wrong timestamp order, not increasing"
             return sched, sched, fwd
         if name != "ddim":
-            raise NotImplementedError(f"scheduler '{name}' is not built in the MI355X engine (built: 'ddim', 'dpm'; 'ddpm' needs the stochastic "
-                                      "DDPM inverse scheduler, outside the etainv hot path)")
+            raise NotImplementedError(f"scheduler '{name}' is not built in the MI355X engine (built: 'ddim', 'dpm'; 'ddpm' is the DDPM inverse "
+                                      "scheduler of the ddpminv / cyclediff inverters, which build it themselves)")
         kw = {"clip_sample": False, "set_alpha_to_one": False, **kw}
         sched = DDIMScheduler.from_config({**model.scheduler.config, **kw})
         sched.set_timesteps(num_inference_steps)

@@ -137,6 +137,46 @@ int etainv_prox_guidance(const float* eps_u, const float* eps_c, float g, int mo
                          float* eps_out, const float* x, float a_from, float a_to, float* x_out, float* thr_out, int n_groups,
                          int rows_per_group, int l, void* stream);
 
+/* ---- edit-friendly DDPM inversion (reference modules/inverse_schedulers/ddpm_inverse_scheduler.py, modules/inversion/ddpm_inversion.py)
+ * All tensors fp32, device, 16-byte aligned; a latent is [4][l][l], chw = 4 l l, 8 <= l <= 96.  The schedule coefficients are float64 HOST tables
+ * that the call reads before it returns (they travel in the kernel arguments): the caller may free them at once.  An element's result depends
+ * on nothing but its own inputs and its step's scalars: not on the step count of the launch, where the chunk starts, n_img or its position.
+ *
+ * etainv_ddpm_sample_latents replaces DDPMInverseScheduler.sample_latents (ddpm_inverse_scheduler.py:86-129), one launch.
+ *   x0 [n_img][chw]; noise [n_steps][n_img][chw] in the reference's draw order (ascending t); ab_host [n_steps][2] = (a, b) per step in that order;
+ *   xts [n_steps + 1][n_img][chw] in the reference's index order: xts[n_steps - 1 - s] belongs to draw s (index 0 = the largest t), xts[n_steps] = x0.
+ *   markovian == 0 (:118): x_t = x0 * a + r * b, a = sqrt(abar_t), b = sqrt(1 - abar_t).  markovian == 1 (:121-125): cur = cur * a + r * b from
+ *   cur = x0, a = sqrt(abar_t / abar_prev), b = sqrt(1 - abar_t / abar_prev); every element walks the steps in its own thread.  Products and sum are
+ *   rounded one by one, as torch does.  1 <= n_steps <= ETAINV_DDPM_MAX_STEPS.
+ *
+ * etainv_ddpm_invert_steps: everything of DDPMInverseScheduler.step (:156-199) after the UNet call for the k consecutive steps
+ *   [first, first + k) of n_img images, one launch.  Step j reads x_t = xts[first + j] and x_{t-1} = xts[first + j + 1] (xts as above, n_steps
+ *   its step count).  eps_u, eps_c [k][n_img][chw]: eps = eps_u + g (eps_c - eps_u); eps_u NULL: eps_c already is the noise, g is ignored.
+ *   coef_host [k][5] = (sqrt(1 - abar_t), sqrt(abar_t), sqrt(abar_prev), sqrt(1 - abar_prev - sigma^2), sigma), sigma = sqrt(get_variance(t)):
+ *     x0_pred = (x_t - c0 eps) / c1;  mu = c2 x0_pred + c3 eps;  z = (x_{t-1} - mu) / sigma;  x_out = mu + sigma z   (:178-196, that operation
+ *   order, every operation rounded to fp32).  Outputs z, x_out, eps_out (the guided noise; may be NULL), each [k][n_img][chw].
+ *   DELIBERATE DEVIATION, sigma == 0: the reference divides by zero there (t = 0 under steps_offset = 0, this pipeline's scheduler): z and the
+ *   latent become NaN / inf.  Here z = 0 and x_out = mu.  The reference zeroes that step's z afterwards (ddpm_inversion.py:101) and never reads
+ *   its latent.  1 <= k <= ETAINV_DDPM_MAX_CHUNK.
+ *
+ * etainv_ddpm_backward_step: everything of DDPMInversion.predict_step_backward (ddpm_inversion.py:135-166) after the UNet call, one launch:
+ *   classifier-free guidance with one scale per prompt (:154-161; the reference's [guidance_scale_fwd, guidance_scale_bwd] for [source, target]
+ *   is n_prompts == 2), then DDIMScheduler.step(eta = 1, variance_noise = z) (:162).  x, eps_u, eps_c, out_x, out_eps (may be NULL):
+ *   [n_prompts * n_img][chw], rows [p0 x n_img, p1 x n_img, ..]; g_host [n_prompts] HOST floats, 1 <= n_prompts <= 4; z [n_img][chw] is shared by
+ *   the prompt rows of an image; a_t, a_p, var as in etainv_ddim_eta_step.  Bit-equal to etainv_cfg_combine per prompt followed by
+ *   etainv_ddim_eta_step(eta = 1, noise = z) per image on fp32 tensors.
+ *
+ * Refused (etainv_last_error says why): a null pointer other than the optional ones, l outside [8, 96], n_steps / k / n_img < 1, a step range
+ * outside the schedule, n_prompts outside [1, 4], a non-finite scale or coefficient, a pointer that is not 16-byte aligned. */
+#define ETAINV_DDPM_MAX_STEPS 256
+#define ETAINV_DDPM_MAX_CHUNK 128
+int etainv_ddpm_sample_latents(const float* x0, const float* noise, const double* ab_host, int markovian, float* xts, int n_steps, int n_img,
+                               int l, void* stream);
+int etainv_ddpm_invert_steps(const float* xts, int n_steps, int first, int k, const float* eps_u, const float* eps_c, float g,
+                             const double* coef_host, float* z, float* x_out, float* eps_out, int n_img, int l, void* stream);
+int etainv_ddpm_backward_step(const float* x, const float* eps_u, const float* eps_c, const float* g_host, int n_prompts, const float* z,
+                              float a_t, float a_p, float var, float* out_x, float* out_eps, int n_img, int l, void* stream);
+
 /* ---- image metrics of saved edits (reference metrics/, compute_metrics.py)
  * The four metrics of EditMetric that need no pretrained network, for b independent pairs in one call: MSEMetric (metrics/metrics.py:7-17),
  * PSNRMetric (:23-34), MSSSIM (metrics/msssim.py:61-106, :168-247 with data_range 1) and SSIM (metrics/ssim.py:8-30, which is
