@@ -507,6 +507,10 @@ int launch_igemm_f32(const IGemmParams& p, hipStream_t s) {
   ETAINV_CHECK(p.rows_per_batch > 0, "rows_per_batch");
   ETAINV_CHECK(!p.ln_stat && !p.stat_out && !p.w_batch_stride, "fp32 path: the LayerNorm / GroupNorm folds are 16-bit-path fusions (the engine runs the standalone norms)");
   ETAINV_CHECK(!p.out_nchw || (p.N == 4 && !p.geglu), "out_nchw needs N == 4");
+  IGemmPlan& plan = igemm_last_plan();
+  plan.route = kIGemmRouteF32;
+  plan.bm = FBM;
+  plan.bn = FBN;
   const double flops = 2.0 * (double)p.M * p.N * (double)(p.taps * (p.c1 + p.c2));
   ProfScope prof(PROF_IGEMM, flops, s, 4.0 * ((double)p.M * (p.c1 + p.c2) + (double)p.N * p.taps * (p.c1 + p.c2) + (double)p.M * p.N));
   hipLaunchKernelGGL(igemm_f32_kernel, dim3(cdiv(p.M, FBM), cdiv(p.N, FBN)), dim3(256), 0, s, p);

@@ -1411,7 +1411,14 @@ bool igemm_hm_ok(const IGemmParams& p, int dtype) {
 // ---- THE dispatch rule of the 16-bit launches (fp32 operands leave launch_igemm before it): the first condition that holds names the kernel -- their order is
 // part of the rule.  Environment switches named here are read per launch
 enum IGemmRoute { ROUTE_PPCONV, ROUTE_DUALN, ROUTE_RING_UPS4, ROUTE_RING_UPS9, ROUTE_RING_PATCH, ROUTE_RING, ROUTE_RING_GEGLU, ROUTE_TWO_SLOT };
-static const char* const kIGemmRouteName[] = {"ppconv", "dualn", "ring-ups4", "ring-ups9", "ring-patch", "ring", "ring-geglu", "two-slot"};   // ETAINV_TRACE_IGEMM, tools/launch_table.py
+static const char* const kIGemmRouteName[] = {"ppconv", "dualn", "ring-ups4", "ring-ups9", "ring-patch", "ring", "ring-geglu", "two-slot", "fp32"};   // ETAINV_TRACE_IGEMM, tools/launch_table.py; "fp32" = kIGemmRouteF32
+static_assert(sizeof(kIGemmRouteName) / sizeof(kIGemmRouteName[0]) == kIGemmRouteF32 + 1, "one name per route and the fp32 twin");
+
+IGemmPlan& igemm_last_plan() {
+  static thread_local IGemmPlan plan;
+  return plan;
+}
+const char* igemm_route_name(int route) { return route >= 0 && route <= kIGemmRouteF32 ? kIGemmRouteName[route] : nullptr; }
 
 static IGemmRoute igemm_route(const IGemmParams& p, int dtype) {
   if (pp_conv_applicable(p, dtype)) return ROUTE_PPCONV;    // ping-pong PATCH conv3x3 (ppconv.hip)
@@ -1467,6 +1474,10 @@ static int launch_two_slot(const IGemmParams& p, int dtype, hipStream_t s, int* 
   }
   static const bool trace = env_on("ETAINV_TRACE_IGEMM");   // behind launch_igemm's line: the tile and the K split this launch takes
   if (trace) fprintf(stderr, "  two-slot tile=%dx%d ksplit=%d\n", bm, bn, ks);
+  IGemmPlan& plan = igemm_last_plan();
+  plan.bm = bm;
+  plan.bn = bn;
+  plan.ksplit = ks;
   IGemmParams pk = p;
   if (ks > 1) {
     // one-time 64 MiB workspace per device.  Launches on one device are serialised by the caller's stream (the engine runs one stream);
@@ -1505,8 +1516,17 @@ static int launch_two_slot(const IGemmParams& p, int dtype, hipStream_t s, int* 
   return 0;
 }
 
-int launch_igemm(const IGemmParams& p_in, int dtype, hipStream_t s, int* stat_P) {
+static int launch_igemm_routed(const IGemmParams& p_in, int dtype, hipStream_t s, int* stat_P);
+int launch_igemm(const IGemmParams& p, int dtype, hipStream_t s, int* stat_P) {
+  const int rc = launch_igemm_routed(p, dtype, s, stat_P);
+  if (rc) igemm_last_plan() = IGemmPlan{};   // a refused launch leaves no plan
+  return rc;
+}
+
+static int launch_igemm_routed(const IGemmParams& p_in, int dtype, hipStream_t s, int* stat_P) {
   if (stat_P) *stat_P = 0;
+  IGemmPlan& plan = igemm_last_plan();
+  plan = IGemmPlan{};
   if (dtype == ETAINV_F32) return launch_igemm_f32(p_in, s);   // fp32-operand parity mode (f32path.hip)
   static void* zero_pages[kMaxDevices] = {};   // 256 zero bytes read by the halo lanes of the 3x3 taps (one-time allocation per device)
   const int dev = current_device();
@@ -1538,6 +1558,9 @@ int launch_igemm(const IGemmParams& p_in, int dtype, hipStream_t s, int* stat_P)
     fprintf(stderr, "igemm M=%d N=%d c1=%d c2=%d taps=%d stride=%d ups=%d H=%d W=%d geglu=%d ln=%d stat=%d res=%d rowvec=%d hm=%d route=%s\n", p.M, p.N, p.c1, p.c2, p.taps,
             p.stride, p.ups, p.H, p.W, (int)p.geglu, p.ln_stat ? 1 : 0, p.stat_out ? p.stat_kind : 0, p.residual ? 1 : 0, p.rowvec ? 1 : 0, p.hm_heads,
             kIGemmRouteName[route]);
+  plan.route = route;   // (the ping-pong launchers and launch_two_slot fill in their tile and form)
+  plan.bm = 256;
+  plan.bn = route == ROUTE_RING_GEGLU ? 128 : 160;
   switch (route) {
     case ROUTE_PPCONV: {
       ProfScope prof(PROF_IGEMM, 2.0 * (double)p.M * (double)p.N * (double)(9 * p.c1), s, igemm_algo_bytes(p));

@@ -99,6 +99,15 @@ inline IGemmParams igemm_conv3x3(const void* a, const void* w, const float* bias
 int launch_igemm(const IGemmParams& p, int dtype, hipStream_t s, int* stat_P = nullptr);
 bool igemm_hm_ok(const IGemmParams& p, int dtype);     // may this launch (with hm_* set) write the head-major layout?
 bool igemm_ups4_ok(const IGemmParams& p, int dtype);   // may this launch run the phase form (ups == 2, taps == 4) of a fused-upsample conv?
+// What the calling thread's last launch_igemm chose (host-side record, no device state; etainv_op_last_igemm_plan hands it to the parity tests):
+// route = index into the route names (kIGemmRouteF32: the fp32 twin; -1: no launch yet, or the launcher refused), the output tile, the K split, and
+// form = 1 for ppconv's dual-M kernel / the epilogue kind 0..3 of a dual-N launch / 0 otherwise
+struct IGemmPlan {
+  int route = -1, bm = 0, bn = 0, ksplit = 1, form = 0;
+};
+constexpr int kIGemmRouteF32 = 8;
+IGemmPlan& igemm_last_plan();
+const char* igemm_route_name(int route);   // nullptr outside 0 .. kIGemmRouteF32
 
 // ---- ppgemm.hip: the dual-N ping-pong GEMM; launch_igemm routes to it when pp_dualn_applicable.
 // dual-N form: a 256 x 320 output tile as two 160-column halves sharing one staged activation K tile (-31 % LDS-DMA bytes per FLOP; the 1x1 GEMMs are bound

@@ -197,6 +197,15 @@ extern "C" int etainv_op_gemm_per_image(const void* a, const void* wb, const flo
   return launch_igemm(p, dtype, (hipStream_t)stream);
 }
 
+// the route, tile and K split of this thread's last launch_igemm (kernels.h: IGemmPlan); no device state, no launch
+extern "C" int etainv_op_last_igemm_plan(int* out, int n) {
+  const IGemmPlan& plan = igemm_last_plan();
+  const int v[5] = {plan.route, plan.bm, plan.bn, plan.ksplit, plan.form};
+  for (int i = 0; i < 5 && i < n; ++i) out[i] = v[i];
+  return 5;
+}
+extern "C" const char* etainv_op_igemm_route_name(int route) { return igemm_route_name(route); }
+
 // timesteps by value in the kernel arguments
 extern "C" int etainv_op_time_embedding(const int64_t* t_host, int rows, int dim, void* out, int dtype, void* stream) {
   return launch_time_embedding(t_host, rows, dim, out, dtype, (hipStream_t)stream);

@@ -840,7 +840,11 @@ int launch_pp_conv(const IGemmParams& p_in, int dtype, hipStream_t s, int* stat_
   ETAINV_CHECK(p.zeros, "zero page");
   if (stat_P) *stat_P = p.stat_out ? 64 : 0;          // GroupNorm partials: rows per row block = the 64-row wave tile
   if (p.stat_out) p.stat_P = 64;
-  if (pp_conv2_ok(p)) {
+  IGemmPlan& plan = igemm_last_plan();
+  plan.bn = CBN;
+  plan.form = pp_conv2_ok(p) ? 1 : 0;
+  plan.bm = plan.form ? 512 : 256;
+  if (plan.form) {
     const int tiles2 = (p.M / 512) * (p.N / CBN);
     const int grid2 = std::min(tiles2, 256);
     ETAINV_DISPATCH_HALF(dtype, T, {

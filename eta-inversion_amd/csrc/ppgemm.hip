@@ -586,6 +586,10 @@ int launch_pp_dualn(const IGemmParams& p_in, int dtype, hipStream_t s, int* stat
   ETAINV_CHECK(kind >= 0, "not a dual-N launch (ask pp_dualn_applicable first)");
   if (p.stat_out) p.stat_P = p.stat_kind == 1 ? 64 : p.N / 80;   // GroupNorm: rows per partial block; LayerNorm: partials per row
   if (stat_P) *stat_P = p.stat_out ? p.stat_P : 0;
+  IGemmPlan& plan = igemm_last_plan();
+  plan.bm = PBM;
+  plan.bn = kind == 3 ? 256 : 320;
+  plan.form = kind;
   const int tiles = (p.M / PBM) * (p.N / (kind == 3 ? 256 : 320));
   static const int grid_cap = std::max(1, env_int("ETAINV_DUALN_GRID", 256));   // (experiments: fewer persistent blocks than CUs)
   const int grid = std::min(tiles, grid_cap);

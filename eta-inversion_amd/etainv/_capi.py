@@ -108,8 +108,10 @@ SIGNATURES = {
     "etainv_op_gn_fold": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _i, _p],
     "etainv_op_gemm_per_image": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "etainv_op_rows_broadcast": [_p, _i, _i, _i64, _i, _p],
+    "etainv_op_last_igemm_plan": [C.POINTER(_i), _i],
+    "etainv_op_igemm_route_name": [_i],
 }
-_RESTYPES = {"etainv_last_error": C.c_char_p, "etainv_engine_workspace_bytes": _i64, "etainv_image_metrics_workspace_bytes": _i64, "etainv_engine_weight_bytes": _i64}
+_RESTYPES = {"etainv_last_error": C.c_char_p, "etainv_op_igemm_route_name": C.c_char_p,"etainv_engine_workspace_bytes": _i64, "etainv_image_metrics_workspace_bytes": _i64, "etainv_engine_weight_bytes": _i64}
 
 _lib = None
 

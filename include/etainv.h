@@ -474,6 +474,12 @@ int etainv_op_gn_fold(const float* w, const float* gamma, const float* beta, con
                       int k, void* wb_out, float* cb_out, int dtype, void* stream);
 int etainv_op_gemm_per_image(const void* a, const void* wb, const float* cb, const void* residual, void* out, int b, int hw, int n, int k,
                              int dtype, void* stream);
+/* Which kernel the calling thread's last GEMM / conv launch (any etainv_op_* above that ends in one, or the engine's) took.  Host-side only: touches no
+ * device state and launches nothing.  Writes up to n of {route, tile rows, tile columns, K split, form} into out and returns how many there are (5):
+ * route indexes etainv_op_igemm_route_name ("ppconv", "dualn", "ring-ups4", "ring-ups9", "ring-patch", "ring", "ring-geglu", "two-slot", "fp32"), -1
+ * before the first launch or after a refused one; form = 1 for ppconv's dual-M kernel, the epilogue kind 0..3 of a dual-N launch, else 0. */
+int etainv_op_last_igemm_plan(int* out, int n);
+const char* etainv_op_igemm_route_name(int route); /* NULL outside the list */
 
 #ifdef __cplusplus
 }

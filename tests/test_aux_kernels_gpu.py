@@ -45,6 +45,23 @@ def assert_guard(buf, rows):
     assert torch.isfinite(buf[:rows]).all(), "the kernel left part of its output unwritten (or wrote a non-finite value)"
 
 
+def last_plan(capi):
+    """what launch_igemm chose for this thread's last launch (etainv_op_last_igemm_plan): route name (None: no launch, or a refused one), tile, K split,
+    form (1: ppconv's dual-M kernel; the epilogue kind of a dual-N launch)"""
+    import ctypes
+    lib, v = capi.load(), (ctypes.c_int * 5)()
+    assert lib.etainv_op_last_igemm_plan(v, 5) == 5
+    name = lib.etainv_op_igemm_route_name(v[0])
+    return dict(route=name.decode() if name else None, bm=v[1], bn=v[2], ksplit=v[3], form=v[4])
+
+
+def two_slot(bm, bn, ksplit):
+    return dict(route="two-slot", bm=bm, bn=bn, ksplit=ksplit, form=0)
+
+
+FP32_PLAN = dict(route="fp32", bm=128, bn=128, ksplit=1, form=0)
+
+
 def rel64(a, b):
     a, b = a.double(), b.double()
     return ((a - b).norm() / b.norm().clamp_min(1e-300)).item()
@@ -68,10 +85,9 @@ def border_errs(out_nhwc, ref_nhwc):
 
 
 # ------------------------------------------------------------------------------------------------ 1. etainv_op_conv3x3_ex
-# Route table (16-bit types; fp32 operands leave launch_igemm for csrc/f32path.hip, one kernel, before the rule and print no launch line).
-# Every case runs on the two-slot kernels (no width is a multiple of 160).  Tile and K split as printed by a run of this file under
-# ETAINV_TRACE_IGEMM=1 (`python -m pytest tests/test_aux_kernels_gpu.py -m gpu -s -v`: behind every launch line a `two-slot tile=... ksplit=...`
-# line), the same for fp16 and bf16:
+# Route table (16-bit types; fp32 operands leave launch_igemm for csrc/f32path.hip, one kernel, before the rule).
+# Every case runs on the two-slot kernels (no width is a multiple of 160).  Tile and K split, the same for fp16 and bf16, are asserted after every launch
+# from what the library reports (last_plan; CONV_PLANS below restates the last two columns):
 #
 #   case                                      M      N    K tiles    tile        ksplit
 #   pad0   2 x  16 x  24  128 -> 128          192    128     18      64 x 64     3
@@ -87,10 +103,11 @@ def border_errs(out_nhwc, ref_nhwc):
 #   ups    1 x  88 x  96  128 -> 128        33792    128     18      128 x 128   1
 #   out_nchw (all 16 cases)               768 / 240    4   18 / 72   64 x 64     1      (out_nchw and split-K exclude each other)
 #
+# out_nchw: test_conv3x3_ex_out_nchw asserts 64 x 64, ksplit 1.
 # So 128 x 128 without split-K, 128 x 128 with it, and 64 x 64 with split-K are each reached by a pad0, a stride-1 and an upsample case.  A
 # 64 x 64 launch of a 3 x 3 conv WITHOUT split-K needs more than 512 small tiles and fewer than 192 big ones, which no VAE shape has: the NCHW
 # cases and the short-K GEMMs of test_gemm_aux_shapes are the unsplit 64 x 64 launches.
-# tests/test_kernels_gpu.py::test_split_k_small_m_deep_k in the same traced run: all four of its launches take the 64 x 64 tile with split-K
+# tests/test_kernels_gpu.py::test_split_k_small_m_deep_k in a run under ETAINV_TRACE_IGEMM=1: all four of its launches take the 64 x 64 tile with split-K
 # (convs M = 64 / 256 / 256, N = 1280: ksplit 30 / 12 / 12; the GEMM (64, 1280, 5120): ksplit 20) -- 8 to 16 tiles of 128 x 160 are far from the
 # 64 that `deep_k` asks for.  So split-K on 64 x 64 tiles was pinned before, for stride-1 convs at N = 1280 with a global norm; what is new here
 # is that path under pad0 and the fused upsample, at N = 128 / 256 / 512, with a ragged M tile, and checked per block and on the border.
@@ -99,6 +116,9 @@ CONV_CASES = [
     ("s1", 2, 64, 48, 512, 512), ("s1", 1, 176, 192, 128, 128), ("s1", 2, 8, 8, 512, 512), ("s1", 3, 10, 12, 128, 256),
     ("ups", 1, 8, 12, 512, 512), ("ups", 2, 32, 48, 256, 256), ("ups", 1, 88, 96, 128, 128),
 ]
+CONV_PLANS = dict(zip(CONV_CASES, [two_slot(64, 64, 3), two_slot(128, 128, 2), two_slot(128, 128, 1), two_slot(64, 64, 9),
+                                   two_slot(128, 128, 2), two_slot(128, 128, 1), two_slot(64, 64, 18), two_slot(64, 64, 3),
+                                   two_slot(64, 64, 18), two_slot(128, 128, 2), two_slot(128, 128, 1)]))
 
 
 def conv_ref64(x, w, bias, mode):
@@ -132,6 +152,7 @@ def test_conv3x3_ex(capi, dtype, mode, b, h, wd, cin, cout):
         ref = ref + res.double().cpu().reshape(b, ho, wo, cout)
     out = guarded(m, cout, dtype)
     conv_ex(capi, x.permute(0, 2, 3, 1).contiguous(), w.permute(0, 2, 3, 1).contiguous(), bias, res, out, b, h, wd, cin, cout, mode, dtype)
+    assert last_plan(capi) == (FP32_PLAN if dtype == torch.float32 else CONV_PLANS[(mode, b, h, wd, cin, cout)])
     assert_guard(out, m)
     got = out[:m].cpu()
     e_all, e_blk = relerr(got, ref.reshape(m, cout)), block_err(got, ref.reshape(m, cout))
@@ -169,6 +190,7 @@ def test_conv3x3_ex_out_nchw(capi, dtype, out_nchw, h, wd, cin):
             out = guarded_flat(n_out, io, 4 * hw)
             conv_ex(capi, x.permute(0, 2, 3, 1).contiguous(), w.permute(0, 2, 3, 1).contiguous(), bias, None, out, b, h, wd, cin, 4, "s1", dtype,
                     out_nchw=out_nchw, io=code)
+            assert last_plan(capi) == (FP32_PLAN if dtype == torch.float32 else two_slot(64, 64, 1))      # (out_nchw and split-K exclude each other)
             torch.cuda.synchronize()
             assert torch.equal(out[n_out:], torch.full_like(out[n_out:], MARK)), "a plane beyond out_nchw was written"
             got = out[:n_out].cpu().reshape(b, out_nchw, h, wd)
@@ -184,8 +206,8 @@ def test_conv3x3_ex_out_nchw(capi, dtype, out_nchw, h, wd, cin):
 
 
 # ------------------------------------------------------------------------------------------------ 2. etainv_op_gemm at VAE and CLIP shapes
-# (m, n, k, kind).  From the same traced run (16-bit types): 128 x 128 without split-K for (24576, 128, 64) and (6144, 512, 256) (192 big tiles
-# each); 64 x 64 for all the others, unsplit except (1024, 512, 1024) (ksplit 4) and the two CLIP shapes with k = 3072 (ksplit 12): split-K needs
+# (m, n, k, kind).  16-bit types (gemm_plan, asserted after every launch): 128 x 128 without split-K for (24576, 128, 64) and (6144, 512, 256) (192 big
+# tiles each); 64 x 64 for all the others, unsplit except (1024, 512, 1024) (ksplit 4) and the two CLIP shapes with k = 3072 (ksplit 12): split-K needs
 # k / 64 >= 16, so k = 512 and k = 768 (12 K tiles) do not split.
 GEMM_CASES = [
     (2 * 16 * 24, 128, 64, "im2col"), (2 * 8 * 12, 512, 64, "im2col"), (24576, 128, 64, "im2col"),
@@ -195,6 +217,12 @@ GEMM_CASES = [
     (360, 256, 128, "shortcut"), (6144, 512, 256, "shortcut"),
     (77, 2304, 768, "clip"), (231, 768, 768, "clip"), (231, 3072, 768, "clip"), (231, 768, 3072, "clip"), (77, 768, 3072, "clip"),
 ]
+
+
+def gemm_plan(m, n, k):
+    if (m, n, k) in ((24576, 128, 64), (6144, 512, 256)):
+        return two_slot(128, 128, 1)
+    return two_slot(64, 64, 4 if (m, n, k) == (1024, 512, 1024) else 12 if k == 3072 else 1)
 
 
 @pytest.mark.parametrize("dtype", DTYPES3)
@@ -215,6 +243,7 @@ def test_gemm_aux_shapes(capi, dtype, m, n, k, kind):
         out = guarded(m, n, dtype)
         capi.check(lib.etainv_op_gemm(capi.ptr(a), capi.ptr(w), capi.ptr(bias if use_b else None), capi.ptr(res if use_r else None), capi.ptr(out),
                                       m, n, k, 0, capi.dtype_code(dtype), capi.stream_ptr()))
+        assert last_plan(capi) == (FP32_PLAN if dtype == torch.float32 else gemm_plan(m, n, k))
         assert_guard(out, m)
         e_all, e_blk = relerr(out[:m], ref), block_err(out[:m], ref)
         print(f"gemm {kind} ({m}, {n}, {k}) {dtype} bias {use_b} residual {use_r}: rel L2 {e_all:.2e}, worst 64x64 block {e_blk:.2e}")

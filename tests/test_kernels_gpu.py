@@ -12,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 from tests import attention_ref as AR
+from tests.gemm_ref import pack_geglu  # noqa: F401  (the GEGLU row interleave; other test modules import it from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -178,15 +179,6 @@ def test_eta_backward_step_batched_images(capi):
 
 
 # ----------------------------------------------------------------------------------------- GEMM / conv
-def pack_geglu(w):
-    """row interleave used by the GEGLU epilogue (csrc/misc.hip pack mode 2)."""
-    rows = w.shape[0]
-    p = torch.arange(rows)
-    blk, within = p // 64, p % 64
-    logical = torch.where(within < 32, blk * 32 + within, rows // 2 + blk * 32 + within - 32)
-    return w[logical]
-
-
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("m,n,k", [(4096, 320, 320), (154, 640, 768), (8192, 960, 320), (64, 1280, 1280), (2, 1280, 320),
                                    (1024, 1280, 5120), (300, 2560, 1280)])
