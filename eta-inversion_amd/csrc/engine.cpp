@@ -145,6 +145,17 @@ struct etainv_engine {
   std::vector<hipStream_t> upload_streams;   // streams weights were uploaded on since the last fold (the fold waits for each that is not the forward's)
   uint64_t ctx_gen = 0, ctx_gen_cached = 0;  // caller's generation of the context buffer (etainv_engine_context_generation)
 
+  // read-only activation taps (etainv_engine_set_tap): one per block of the UNet graph, named by the oracle module whose output it is, in execution
+  // order.  A set tap makes the forward copy the block's output to `dst` right after the block; `rows` = the rows that were live there in the last forward
+  struct Tap { std::string name; int side = 1, channels = 0; void* dst = nullptr; int rows = 0; };
+  std::vector<Tap> taps;
+  int tap_index(const std::string& name) const {
+    for (size_t i = 0; i < taps.size(); ++i)
+      if (taps[i].name == name) return (int)i;
+    return -1;
+  }
+  size_t tap_bytes(const Tap& t, int rows) const { return (size_t)rows * t.side * t.side * t.channels * esz; }
+
   long long qkv_hm_launches = 0;      // fused QKV projections that wrote the head-major layout since creation
   bool qkv_hm = true;                 // fused QKV projections write head-major planes where the GEMM and the attention kernel both can (ETAINV_QKV_HM)
 };
@@ -370,6 +381,49 @@ int build_model(etainv_engine* e) {
   return 0;
 }
 
+// the tap points: every block of the graph build_model registered, under the oracle's module names (oracle/unet.py), in execution order
+void build_taps(etainv_engine* e) {
+  const int L = e->L;
+  const int ch[4] = {320, 640, 1280, 1280};
+  auto add = [&](const std::string& name, int side, int c) {
+    etainv_engine::Tap t;
+    t.name = name;
+    t.side = side;
+    t.channels = c;
+    e->taps.push_back(t);
+  };
+  add("time_embedding", 1, etainv_engine::kTemb);   // [rows][1280]: the MLP output in front of the in-place SiLU
+  add("conv_in", L, ch[0]);
+  int side = L;
+  for (int i = 0; i < 4; ++i) {
+    const std::string b = "down_blocks." + std::to_string(i);
+    for (int j = 0; j < 2; ++j) {
+      add(b + ".resnets." + std::to_string(j), side, ch[i]);
+      if (i < 3) add(b + ".attentions." + std::to_string(j), side, ch[i]);
+    }
+    if (i < 3) {
+      side /= 2;
+      add(b + ".downsamplers.0", side, ch[i]);
+    }
+  }
+  add("mid_block.resnets.0", side, 1280);
+  add("mid_block.attentions.0", side, 1280);
+  add("mid_block.resnets.1", side, 1280);
+  const int rev[4] = {1280, 1280, 640, 320};
+  for (int i = 0; i < 4; ++i) {
+    const std::string b = "up_blocks." + std::to_string(i);
+    for (int j = 0; j < 3; ++j) {
+      add(b + ".resnets." + std::to_string(j), side, rev[i]);
+      if (i > 0) add(b + ".attentions." + std::to_string(j), side, rev[i]);
+    }
+    if (i < 3) {
+      side *= 2;
+      add(b + ".upsamplers.0", side, rev[i]);
+    }
+  }
+  add("conv_norm_out", L, ch[0]);                    // GroupNorm + SiLU in gnbuf: what conv_out reads
+}
+
 int build_workspace(etainv_engine* e) {
   ArenaPlan plan;
   std::vector<std::function<void(char*)>> fix;
@@ -443,6 +497,18 @@ struct Fwd {
     for (int i = 0; i < 16; ++i)
       if (e->gn_bufs[i] == buf) return i;
     return -1;
+  }
+  // tap point `name`: `n` rows of `buf` are the block's output (a set tap copies them out; the row count is recorded either way)
+  int tap(const std::string& name, const void* buf, int n) {
+    const int i = e->tap_index(name);
+    if (i < 0) {
+      set_error("unknown tap point " + name);
+      return 1;
+    }
+    etainv_engine::Tap& t = e->taps[i];
+    t.rows = n;
+    if (t.dst) ETAINV_HIP(hipMemcpyAsync(t.dst, buf, e->tap_bytes(t, n), hipMemcpyDeviceToDevice, s));
+    return 0;
   }
   // launch + bookkeeping: gn_out asks the epilogue for the GroupNorm partials of p.out (when the launch shape can: launch_igemm reports the rows
   // per block, 0 otherwise)
@@ -674,6 +740,7 @@ extern "C" int etainv_engine_create(const etainv_engine_config* cfg, etainv_engi
   e->ln_fused = !env_on("ETAINV_LN_UNFUSED") && e->dt != ETAINV_F32;
   e->gn_fused = !env_on("ETAINV_GN_UNFUSED") && e->dt != ETAINV_F32;
   e->qkv_hm = env_flag("ETAINV_QKV_HM", true);   // (default on: +0.8 % on the benchmark step, +1 % on config 5; "0" = row-major)
+  build_taps(e);
   if (build_model(e) || build_workspace(e)) {
     etainv_engine_destroy(e);
     return 1;
@@ -774,6 +841,32 @@ extern "C" int etainv_engine_qkv_head_major_count(etainv_engine_t* e, long long*
   return 0;
 }
 
+extern "C" int etainv_engine_tap_count(etainv_engine_t* e) { return e ? (int)e->taps.size() : 0; }
+
+extern "C" int etainv_engine_tap_info(etainv_engine_t* e, int point, char* name, int name_cap, int* side, int* channels) {
+  ETAINV_CHECK(e && point >= 0 && point < (int)e->taps.size() && name && side && channels, "bad arguments");
+  const etainv_engine::Tap& t = e->taps[point];
+  ETAINV_CHECK((int)t.name.size() + 1 <= name_cap, "name buffer too small");
+  std::memcpy(name, t.name.c_str(), t.name.size() + 1);
+  *side = t.side;
+  *channels = t.channels;
+  return 0;
+}
+
+extern "C" int etainv_engine_set_tap(etainv_engine_t* e, int point, void* dst, int64_t capacity_bytes) {
+  ETAINV_CHECK(e && point >= 0 && point < (int)e->taps.size(), "bad arguments");
+  etainv_engine::Tap& t = e->taps[point];
+  // (every forward of this engine fits: no call can find the buffer too small after it has enqueued work)
+  ETAINV_CHECK(!dst || capacity_bytes >= (int64_t)e->tap_bytes(t, e->maxB), "tap buffer smaller than max_unet_batch rows of " + t.name);
+  t.dst = dst;
+  return 0;
+}
+
+extern "C" int etainv_engine_tap_rows(etainv_engine_t* e, int point) {
+  if (!e || point < 0 || point >= (int)e->taps.size()) return -1;
+  return e->taps[point].rows;
+}
+
 extern "C" int etainv_unet_forward(etainv_engine_t* e, const void* latent, int n_lat, const int64_t* t_host, const void* ctx, int n_rows,
                                    const etainv_attn_ctrl* ctrl, void* out, int io_dtype, void* stream) {
   ETAINV_CHECK(e && latent && t_host && ctx && out, "null argument");
@@ -805,12 +898,14 @@ extern "C" int etainv_unet_forward(etainv_engine_t* e, const void* latent, int n
   if (e->ln_fused && !e->ln_folded && fold_layernorms(e, s)) return 1;
   Fwd f{e, s, n_rows, ctrl};
   f.ctx_rows = n_rows;
+  for (auto& t : e->taps) t.rows = 0;
 
   // timesteps (by value in the kernel arguments: no host buffer outlives this call) -> embedding, MLP, all 22 projections in one GEMM
   if (launch_time_embedding(t_host, n_rows, etainv_engine::kCh0, e->tembuf, e->dt, s)) return 1;
   if (f.run(Fwd::linear(e->tembuf, e->time1, e->temb1, n_rows))) return 1;
   if (launch_silu(e->temb1, e->temb1, (int64_t)n_rows * etainv_engine::kTemb, e->dt, s)) return 1;
   if (f.run(Fwd::linear(e->temb1, e->time2, e->temb2, n_rows))) return 1;
+  if (f.tap("time_embedding", e->temb2, n_rows)) return 1;
   if (launch_silu(e->temb2, e->temb2, (int64_t)n_rows * etainv_engine::kTemb, e->dt, s)) return 1;
   {
     IGemmParams p = Fwd::linear(e->temb2, e->tproj, e->tprojbuf, n_rows);
@@ -843,7 +938,9 @@ extern "C" int etainv_unet_forward(etainv_engine_t* e, const void* latent, int n
   const void* h = e->skip[0];
   int hc = 320;
   for (int i = 0; i < 4; ++i) {
+    const std::string blk = "down_blocks." + std::to_string(i);
     for (int j = 0; j < 2; ++j) {
+      const std::string rname = blk + ".resnets." + std::to_string(j);
       if (i < 3) {
         void* r_out = pick_tmp(e, h, nullptr);
         if (f.resblock(e->res[ri++], h, nullptr, hc, 0, side, r_out)) return 1;
@@ -852,9 +949,13 @@ extern "C" int etainv_unet_forward(etainv_engine_t* e, const void* latent, int n
           if (f.dup_rows(e->skip[0], pre_rows, dup_n, L * L, etainv_engine::kCh0) || f.dup_rows(r_out, pre_rows, dup_n, L * L, ch[0])) return 1;
         }
         f.rows = n_rows;
+        // (behind dup_rows: the taps of a shared prefix hold all rows)
+        if ((first && f.tap("conv_in", e->skip[0], n_rows)) || f.tap(rname, r_out, n_rows)) return 1;
         if (f.transformer(e->tb[ti++], r_out, side, e->skip[si], first && share ? pre_rows : 0)) return 1;
+        if (f.tap(blk + ".attentions." + std::to_string(j), e->skip[si], f.rows)) return 1;
       } else {
         if (f.resblock(e->res[ri++], h, nullptr, hc, 0, side, e->skip[si])) return 1;
+        if (f.tap(rname, e->skip[si], f.rows)) return 1;
       }
       h = e->skip[si++];
       hc = ch[i];
@@ -863,16 +964,17 @@ extern "C" int etainv_unet_forward(etainv_engine_t* e, const void* latent, int n
       if (f.run_conv(f.conv3x3(h, e->down_conv[i], e->skip[si], side, /*stride=*/2, /*ups=*/0), e->down_conv[i])) return 1;
       h = e->skip[si++];
       side /= 2;
+      if (f.tap(blk + ".downsamplers.0", h, f.rows)) return 1;
     }
   }
   // ---- mid
   {
     void* a = pick_tmp(e, h, nullptr);
-    if (f.resblock(e->res[ri++], h, nullptr, 1280, 0, side, a)) return 1;
+    if (f.resblock(e->res[ri++], h, nullptr, 1280, 0, side, a) || f.tap("mid_block.resnets.0", a, f.rows)) return 1;
     void* b2 = pick_tmp(e, a, nullptr);
-    if (f.transformer(e->tb[ti++], a, side, b2)) return 1;
+    if (f.transformer(e->tb[ti++], a, side, b2) || f.tap("mid_block.attentions.0", b2, f.rows)) return 1;
     void* c = pick_tmp(e, b2, nullptr);
-    if (f.resblock(e->res[ri++], b2, nullptr, 1280, 0, side, c)) return 1;
+    if (f.resblock(e->res[ri++], b2, nullptr, 1280, 0, side, c) || f.tap("mid_block.resnets.1", c, f.rows)) return 1;
     h = c;
     hc = 1280;
   }
@@ -882,17 +984,20 @@ extern "C" int etainv_unet_forward(etainv_engine_t* e, const void* latent, int n
   int sp = 11;
   for (int i = 0; i < 4; ++i) {
     const int cout = rev[i];
+    const std::string blk = "up_blocks." + std::to_string(i);
     for (int j = 0; j < 3; ++j) {
       const void* sk = e->skip[sp];
       const int skc = skip_c[sp];
       --sp;
       void* r_out = pick_tmp(e, h, nullptr);
       if (f.resblock(e->res[ri++], h, sk, hc, skc, side, r_out, /*pnp_site=*/i == 1 && j == 1)) return 1;
+      if (f.tap(blk + ".resnets." + std::to_string(j), r_out, f.rows)) return 1;
       h = r_out;
       hc = cout;
       if (i > 0) {
         void* t_out = pick_tmp(e, h, nullptr);
         if (f.transformer(e->tb[ti++], h, side, t_out)) return 1;
+        if (f.tap(blk + ".attentions." + std::to_string(j), t_out, f.rows)) return 1;   // (all rows: an exit takes effect behind this block)
         h = t_out;
         // the cond source rows (last n_img of [u_t, c_t, c_s]) have fed their last stored attention layer: everything after runs on the other rows
         if (ctrl && ctrl->src_exit_block && ti == ctrl->src_exit_block + 1) f.rows = 2 * ctrl->n_img;
@@ -903,10 +1008,12 @@ extern "C" int etainv_unet_forward(etainv_engine_t* e, const void* latent, int n
       if (f.run_conv(f.conv3x3(h, e->up_conv[i], u, side, /*stride=*/1, /*ups=*/1), e->up_conv[i])) return 1;
       h = u;
       side *= 2;
+      if (f.tap(blk + ".upsamplers.0", u, f.rows)) return 1;
     }
   }
   // ---- out
   if (f.groupnorm(h, nullptr, 320, 0, e->norm_out, L * L, 1e-5f, 1)) return 1;
+  if (f.tap("conv_norm_out", e->gnbuf, f.rows)) return 1;
   IGemmParams p = igemm_conv3x3(e->gnbuf, e->conv_out_w, e->conv_out_b, out, f.rows, L, L, 320, 4, /*stride=*/1, /*ups=*/0);
   p.out_nchw = 4;
   p.out_io_dtype = io_dtype;

@@ -158,6 +158,49 @@ class Engine:
         finally:
             self.cache_context(False)
 
+    # ------------------------------------------------------------------ activation taps (per-block parity tests)
+    def tap_specs(self):
+        """[(name, side, channels)] of the tap points in execution order; a tapped tensor is NHWC (rows, side * side, channels) in the compute dtype"""
+        out = []
+        name, side, ch = C.create_string_buffer(128), C.c_int(), C.c_int()
+        for i in range(self.lib.etainv_engine_tap_count(self.h)):
+            _capi.check(self.lib.etainv_engine_tap_info(self.h, i, name, 128, C.byref(side), C.byref(ch)))
+            out.append((name.value.decode(), side.value, ch.value))
+        return out
+
+    def tap_names(self):
+        return [n for n, _, _ in self.tap_specs()]
+
+    def tap_rows(self, name):
+        """rows that were live at the tap point in the last forward (fewer than the call's behind a src_exit_block)"""
+        return self.lib.etainv_engine_tap_rows(self.h, self.tap_names().index(name))
+
+    @contextlib.contextmanager
+    def tapped(self, names=None):
+        """`with engine.tapped() as taps:` -- every `engine.unet` call inside also copies the output of each named block (default: all of
+        `tap_names()`) into buffers owned by the context; `taps()` returns {name: tensor (rows, side * side, channels)} of the last call, cloned,
+        with the rows that were live at each point.  The taps are cleared on every exit path."""
+        specs = self.tap_specs()
+        want = {n for n, _, _ in specs} if names is None else set(names)
+        unknown = want - {n for n, _, _ in specs}
+        if unknown:
+            raise KeyError(f"no such tap point: {sorted(unknown)}")
+        bufs = {}
+        try:
+            for i, (n, side, ch) in enumerate(specs):
+                if n in want:
+                    buf = torch.empty(self.max_unet_batch, side * side, ch, dtype=self.dtype, device=self.device)
+                    _capi.check(self.lib.etainv_engine_set_tap(self.h, i, _capi.ptr(buf), buf.numel() * buf.element_size()))
+                    bufs[n] = (i, buf)
+
+            def read():
+                return {n: buf[:self.lib.etainv_engine_tap_rows(self.h, i)].clone() for n, (i, buf) in bufs.items()}
+            yield read
+        finally:
+            torch.cuda.current_stream().synchronize()      # (the buffers are freed below: no copy may still be in flight)
+            for i, _ in bufs.values():
+                self.lib.etainv_engine_set_tap(self.h, i, None, 0)
+
     def local_blend(self, x, n_img, blend_alpha, thres=0.3):
         assert x.dtype == torch.float32
         _capi.check(self.lib.etainv_local_blend(self.h, _capi.ptr(x), n_img, _capi.ptr(blend_alpha), float(thres), _capi.stream_ptr()))

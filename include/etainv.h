@@ -330,6 +330,20 @@ int etainv_engine_context_generation(etainv_engine_t* e, uint64_t generation);
  * whole 256-row tiles inside one batch row), so that a 64-key tile is one contiguous block.  Same values, same arithmetic: results are bit-identical.
  * `launches` = how many QKV projections took that path since the engine was created. */
 int etainv_engine_qkv_head_major_count(etainv_engine_t* e, long long* launches);
+/* Read-only activation taps of etainv_unet_forward (per-block parity tests: tests/test_unet_blocks_gpu.py).  The tap points are the blocks of the
+ * UNet graph in execution order, each named by the module of the diffusers UNet whose output it is: `time_embedding` (the [rows][1280] MLP output in
+ * front of the SiLU), `conv_in`, `down_blocks.{i}.resnets.{j}` / `.attentions.{j}` / `.downsamplers.0`, `mid_block.resnets.0` / `.attentions.0` /
+ * `.resnets.1`, `up_blocks.{i}.resnets.{j}` / `.attentions.{j}` / `.upsamplers.0`, `conv_norm_out` (GroupNorm + SiLU: what conv_out reads).
+ * etainv_engine_tap_info: name, pixels per side and channels of one point; a tapped tensor is NHWC [rows][side * side][channels] in the compute dtype.
+ * etainv_engine_set_tap: `dst` is device memory of at least max_unet_batch rows (refused otherwise, here and not in a forward); NULL clears the tap.
+ * A set tap makes every forward enqueue one device-to-device copy of the block's output on the call's stream right after the block (behind the row
+ * duplication where the context-independent prefix ran on half the rows); the forward's result does not change, and a forward without taps enqueues
+ * nothing more than it did.  etainv_engine_tap_rows: the rows that were live at the point in the last forward (fewer than n_rows behind a
+ * src_exit_block), set or not; -1 for a bad argument. */
+int etainv_engine_tap_count(etainv_engine_t* e);
+int etainv_engine_tap_info(etainv_engine_t* e, int point, char* name, int name_cap, int* side, int* channels);
+int etainv_engine_set_tap(etainv_engine_t* e, int point, void* dst, int64_t capacity_bytes);
+int etainv_engine_tap_rows(etainv_engine_t* e, int point);
 int64_t etainv_engine_workspace_bytes(etainv_engine_t* e);
 int64_t etainv_engine_weight_bytes(etainv_engine_t* e);
 

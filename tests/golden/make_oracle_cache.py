@@ -22,7 +22,8 @@ for p in (ROOT, ROOT / "eta-inversion_amd"):
 
 import torch  # noqa: E402
 
-LEG_MODULES = ["tests.test_unet_gpu", "tests.test_e2e_gpu", "tests.test_fp32_gpu", "tests.test_realsize_gpu", "tests.test_configs_gpu"]
+LEG_MODULES = ["tests.test_unet_gpu", "tests.test_e2e_gpu", "tests.test_fp32_gpu", "tests.test_realsize_gpu", "tests.test_configs_gpu",
+               "tests.test_unet_blocks_gpu"]
 
 
 def import_legs():
