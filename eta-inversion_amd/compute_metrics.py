@@ -3,13 +3,17 @@
 
     python compute_metrics.py --data_path data/eval/PIE-Bench_v1 --output result/pie_etainv_ptp [--metric mse psnr ssim msssim]
                               [--batch 32] [--device cuda|cpu] [--size 512] [--limit N] [--categories 1_change_object ...]
+                              [--clip_weights PATH|synthetic] [--clip_tokenizer DIR] [--clip_templates FILE] [--clip_model ViT-B/16]
 
 Reads the layout eval.py writes, `<output>/imgs/{i:04d}_{source}_{target}.png`, next to the data set's source images.  Kept from the reference:
 one `<output>/metrics/<name>.yaml` per metric, {name, mean, results: [{value, file}]}; a metric whose yaml exists is skipped (the file is
 created exclusively before any work, so two runs never compute the same metric); a sample whose source or edited file is missing is skipped
 with a message; a sample whose metric raises gets nan; both images go through StablePreprocess(size, center_crop=True).  Different by design:
 samples are processed --batch at a time, all wanted metrics of a batch in one `image_metrics` call, and the default metric list is the four
-that are built (EditMetric refuses the others by name)."""
+that are built (EditMetric refuses the others by name).  The CLIP metrics (clip_text_img, clip_img_img, clip_textdir_imgdir, clip_text_img_acc) are
+computed only when --clip_weights hands their weights over (a transformers CLIPModel state dict or an OpenAI clip checkpoint; "synthetic" with
+--clip_model for dry runs): the data set's prompts go with every pair into one `clip_scores` call per batch.  --clip_templates FILE: one caption
+template per line, each with a {} for the prompt."""
 import argparse
 import sys
 from pathlib import Path
@@ -20,6 +24,7 @@ import yaml
 HERE = Path(__file__).resolve().parent
 sys.path.insert(0, str(HERE))
 from dataset.pie_bench_data import PieBenchData, edit_image_name  # noqa: E402
+from metrics import NAMES as IMAGE_NAMES  # noqa: E402
 from metrics import EditMetric, image_metrics  # noqa: E402
 
 
@@ -34,6 +39,12 @@ def parse_args(argv=None):
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--limit", type=int, default=None)
     ap.add_argument("--categories", nargs="+", default=None)
+    ap.add_argument("--clip_weights", default=None, help="CLIP weights (a CLIPModel state dict, an OpenAI clip checkpoint, or 'synthetic'); "
+                    "without it the clip_* metrics are refused")
+    ap.add_argument("--clip_templates", default=None, help="file with one caption template per line, each with a {} for the prompt")
+    ap.add_argument("--clip_model", default="ViT-B/16", help="geometry of --clip_weights synthetic")
+    ap.add_argument("--clip_tokenizer", default=None, help="directory with CLIP's vocab.json and merges.txt (default: ETAINV_SD_PATH/tokenizer); "
+                    "trained weights are refused without one")
     return ap.parse_args(argv)
 
 
@@ -51,18 +62,32 @@ def _claim(metric_dir: Path, metrics):
     return mine
 
 
-def _values(names, edits, sources):
+def _compute(names, edits, sources, prompts, clip):
+    """{name: tensor [B]} of one batch: the image metrics in one `image_metrics` call, the CLIP metrics in one `clip_scores` call"""
+    out = {}
+    image = [n for n in names if n in IMAGE_NAMES]
+    if image:
+        out.update(image_metrics(torch.cat(edits), torch.cat(sources), (-1, 1), image))
+    other = [n for n in names if n not in IMAGE_NAMES]
+    if other:
+        from metrics import clip_scores
+        out.update(clip_scores(torch.cat(edits), torch.cat(sources), [p[0] for p in prompts], [p[1] for p in prompts], other, clip, (-1, 1)))
+    return out
+
+
+def _values(names, edits, sources, prompts=None, clip=None):
     """{name: [float per pair]}: one call for the batch; if it raises, pair by pair and metric by metric, nan where that raises"""
+    prompts = prompts or [("", "")] * len(edits)
     try:
-        out = image_metrics(torch.cat(edits), torch.cat(sources), (-1, 1), names)
+        out = _compute(names, edits, sources, prompts, clip)
         return {n: [float(v) for v in out[n].cpu()] for n in names}
     except Exception:
         pass
     vals = {n: [] for n in names}
-    for e, s in zip(edits, sources):
+    for e, s, p in zip(edits, sources, prompts):
         for n in names:
             try:
-                vals[n].append(float(image_metrics(e, s, (-1, 1), (n,))[n][0]))
+                vals[n].append(float(_compute((n,), [e], [s], [p], clip)[n][0]))
             except Exception as exc:
                 print(f"{n}: nan because of {exc}")
                 vals[n].append(float("nan"))
@@ -73,7 +98,18 @@ def _values(names, edits, sources):
 def main(argv=None):
     a = parse_args(argv)
     device = a.device or ("cuda" if torch.cuda.is_available() else "cpu")
-    metrics = [EditMetric(m, input_range=(-1, 1), device=device) for m in (a.metric or EditMetric.get_built_metrics())]
+    clip = None
+    if a.clip_weights is not None and any(m.startswith("clip_") for m in (a.metric or [])):
+        from metrics import ClipModel
+        templates = None
+        if a.clip_templates is not None:
+            with open(a.clip_templates) as fh:
+                templates = [line.rstrip("\n") for line in fh if line.strip()]
+        clip = ClipModel(a.clip_weights, device, a.clip_model, templates=templates, tokenizer=a.clip_tokenizer)
+        if any(m != "clip_img_img" for m in a.metric if m.startswith("clip_")):
+            clip.tokenize(["a"])                                 # trained weights without a CLIP tokenizer: refused here, before any yaml is claimed
+    metrics = [EditMetric(m, input_range=(-1, 1), device=device, **({"clip_weights": clip} if clip is not None and m.startswith("clip_") else {}))
+               for m in (a.metric or EditMetric.get_built_metrics())]
     metric_dir = Path(a.output) / "metrics"
     metric_dir.mkdir(parents=True, exist_ok=True)
     mine = _claim(metric_dir, metrics)
@@ -85,15 +121,15 @@ def main(argv=None):
     data = PieBenchData(a.data_path, skip_img_load=True, limit=a.limit, categories=a.categories)
     results = {n: [] for n in names}
 
-    def flush(stems, edits, sources):
+    def flush(stems, edits, sources, prompts):
         if not stems:
             return
-        vals = _values(names, edits, sources)
+        vals = _values(names, edits, sources, prompts, clip)
         for (m, _), n in zip(mine, names):
             m.metric.losses.extend(vals[n])                      # what EditMetric.update records, for the whole batch
             results[n].extend({"value": v, "file": stem} for v, stem in zip(vals[n], stems))
 
-    stems, edits, sources = [], [], []
+    stems, edits, sources, prompts = [], [], [], []
     for i in range(len(data)):
         s = data[i]
         edit_file = Path(a.output) / "imgs" / f"{edit_image_name(i, s['source_prompt'], s['edit']['target_prompt'])}.png"
@@ -104,8 +140,8 @@ def main(argv=None):
             e, src = preproc(edit_file), preproc(s["image_file"])
         except Exception as exc:                                 # an unreadable file: the sample's metrics "raise" (reference :97-107)
             print(f"Skipping {s['image_file']} because of {exc}")
-            flush(stems, edits, sources)                         # (keeps the results in data-set order)
-            stems, edits, sources = [], [], []
+            flush(stems, edits, sources, prompts)                # (keeps the results in data-set order)
+            stems, edits, sources, prompts = [], [], [], []
             for (m, _), n in zip(mine, names):
                 m.metric.losses.append(float("nan"))
                 results[n].append({"value": float("nan"), "file": edit_file.stem})
@@ -113,10 +149,11 @@ def main(argv=None):
         stems.append(edit_file.stem)
         edits.append(e)
         sources.append(src)
+        prompts.append((s["source_prompt"], s["edit"]["target_prompt"]))
         if len(stems) == a.batch:
-            flush(stems, edits, sources)
-            stems, edits, sources = [], [], []
-    flush(stems, edits, sources)
+            flush(stems, edits, sources, prompts)
+            stems, edits, sources, prompts = [], [], [], []
+    flush(stems, edits, sources, prompts)
     for (m, f), n in zip(mine, names):
         res = {"name": n, "mean": m.compute()[0] if results[n] else float("nan"), "results": results[n]}
         with open(f, "w") as fh:

@@ -3,7 +3,7 @@
 set -e
 HERE="$(cd "$(dirname "$0")" && pwd)"
 OUT="$HERE/../etainv/lib"
-OBJ="$HERE/obj"; LIBNAME=libetainv_hip.so; SRCS="step_kernels ddpm regularize proximal metrics igemm norm attention misc maps aux_nets f32path ppgemm ppconv"
+OBJ="$HERE/obj"; LIBNAME=libetainv_hip.so; SRCS="step_kernels ddpm regularize proximal metrics clip igemm norm attention misc maps aux_nets f32path ppgemm ppconv"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result"
 mkdir -p "$OUT" "$OBJ"
 pids=()

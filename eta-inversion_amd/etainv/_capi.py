@@ -49,6 +49,11 @@ SIGNATURES = {
     "etainv_ddpm_backward_step": [_p, _p, _p, _p, _i, _p, _f, _f, _f, _p, _p, _i, _i, _p],
     "etainv_image_metrics_workspace_bytes": [_i, _i, _i, _i],
     "etainv_image_metrics": [_p, _p, _i, _i, _i, _f, _f, _i, _p, _p, _i64, _p],
+    "etainv_clip_preprocess": [_p, _i, _i, _i, _i, _f, _f, _p, _p, _i, _p, _p, _i, _i, _p, _p, _i, _p],
+    "etainv_clip_assemble_tokens": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "etainv_op_vit_attention": [_p, _p, _i, _i, _i, _i, _i, _p],
+    "etainv_clip_embed_head": [_p, _i, _p, _i, _i, _i, _p, _p, _f, _p, _i, _i, _p, _p],
+    "etainv_clip_similarity": [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p],
     "etainv_engine_create": [C.POINTER(EngineConfig), C.POINTER(_p)],
     "etainv_engine_destroy": [_p],
     "etainv_engine_num_weights": [_p],

@@ -11,7 +11,7 @@ import zlib
 import torch
 
 from . import _capi
-from .weights import synthetic_tensor
+from .weights import synthetic_clip_tensor, synthetic_tensor
 
 
 def _dev(t, dtype):
@@ -276,3 +276,117 @@ class NativeCLIPText:
             _capi.check(o.lib.etainv_op_quick_gelu(_capi.ptr(f), _capi.ptr(f), f.numel(), o.code, o.st()))
             x = o.gemm(f, *l["fc2"], residual=x)
         return (o.ln(x, *self.final_ln).reshape(b, n, d).float(),)
+
+
+class NativeCLIPVision:
+    """CLIP's ViT image tower (transformers `CLIPModel` names under `vision_model.`): patch-embedding GEMM on the rows etainv_clip_preprocess
+    writes, class token + position embeddings, pre_layrnorm, and the encoder layers of NativeCLIPText with etainv_op_vit_attention in place of the
+    causal kernel.  Any width that is a multiple of 64, heads = width / 64.  Returns the encoder's output; post_layernorm runs in the embedding head
+    (etainv_clip_embed_head), on the pooled token only."""
+
+    def __init__(self, state_dict=None, compute_dtype=torch.float16, seed=0, layers=12, d=768, patch=16, image=224):
+        if d % 64 or patch not in (14, 16, 32) or image % patch:
+            raise ValueError(f"NativeCLIPVision: width {d} must be a multiple of 64, patch {patch} one of 14, 16, 32 and divide the image size {image}")
+        self.ops, self.cd, self.d, self.heads, self.patch, self.image = _Ops(compute_dtype), compute_dtype, d, d // 64, patch, image
+        self._sd, self._seed = state_dict, seed
+        g = self._get
+        pre = "vision_model."
+        f32 = torch.float32
+        self.g2 = (image // patch) ** 2
+        k = 3 * patch * patch
+        self.kp = (k + 63) // 64 * 64
+        w = torch.zeros(d, self.kp)
+        w[:, :k] = g(pre + "embeddings.patch_embedding.weight", (d, 3, patch, patch)).reshape(d, k)
+        self.patch_w = _dev(w, compute_dtype)
+        self.cls = _dev(g(pre + "embeddings.class_embedding", (d,)), compute_dtype)
+        self.pos = _dev(g(pre + "embeddings.position_embedding.weight", (self.g2 + 1, d)), compute_dtype)
+        self.pre_ln = (_dev(g(pre + "pre_layrnorm.weight", (d,)), f32), _dev(g(pre + "pre_layrnorm.bias", (d,)), f32))
+        self.layers = []
+        for i in range(layers):
+            p = f"{pre}encoder.layers.{i}."
+            wq, wk, wv = (g(p + f"self_attn.{n}.weight", (d, d)) for n in ("q_proj", "k_proj", "v_proj"))
+            bq, bk, bv = (g(p + f"self_attn.{n}.bias", (d,)) for n in ("q_proj", "k_proj", "v_proj"))
+            self.layers.append({
+                "ln1": (_dev(g(p + "layer_norm1.weight", (d,)), f32), _dev(g(p + "layer_norm1.bias", (d,)), f32)),
+                "qkv": (_dev(torch.cat([wq, wk, wv]), compute_dtype), _dev(torch.cat([bq, bk, bv]), f32)),
+                "out": (_dev(g(p + "self_attn.out_proj.weight", (d, d)), compute_dtype), _dev(g(p + "self_attn.out_proj.bias", (d,)), f32)),
+                "ln2": (_dev(g(p + "layer_norm2.weight", (d,)), f32), _dev(g(p + "layer_norm2.bias", (d,)), f32)),
+                "fc1": (_dev(g(p + "mlp.fc1.weight", (4 * d, d)), compute_dtype), _dev(g(p + "mlp.fc1.bias", (4 * d,)), f32)),
+                "fc2": (_dev(g(p + "mlp.fc2.weight", (d, 4 * d)), compute_dtype), _dev(g(p + "mlp.fc2.bias", (d,)), f32))})
+        self.post_ln = (_dev(g(pre + "post_layernorm.weight", (d,)), f32), _dev(g(pre + "post_layernorm.bias", (d,)), f32))
+
+    def _get(self, name, shape):
+        if self._sd is not None:
+            t = self._sd[name].float()
+            assert tuple(t.shape) == tuple(shape), (name, t.shape, shape)
+            return t
+        return synthetic_clip_tensor(name, shape, self._seed)
+
+    def __call__(self, rows, b):
+        """patch rows [b g^2][Kp] (compute dtype, from etainv_clip_preprocess) -> hidden states [b][1 + g^2][d] (compute dtype)"""
+        o, d, n = self.ops, self.d, self.g2 + 1
+        assert rows.shape == (b * self.g2, self.kp) and rows.dtype == self.cd, (rows.shape, rows.dtype)
+        pe = o.gemm(rows, self.patch_w)
+        x = torch.empty(b * n, d, dtype=self.cd, device="cuda")
+        _capi.check(o.lib.etainv_clip_assemble_tokens(_capi.ptr(pe), _capi.ptr(self.cls), _capi.ptr(self.pos), _capi.ptr(x), b, self.g2, d, o.code, o.st()))
+        x = o.ln(x, *self.pre_ln)
+        for l in self.layers:
+            qkv = o.gemm(o.ln(x, *l["ln1"]), *l["qkv"])
+            att = torch.empty(b * n, d, dtype=self.cd, device="cuda")
+            _capi.check(o.lib.etainv_op_vit_attention(_capi.ptr(qkv), _capi.ptr(att), b, n, self.heads, 64, o.code, o.st()))
+            x = o.gemm(att, *l["out"], residual=x)
+            f = o.gemm(o.ln(x, *l["ln2"]), *l["fc1"])
+            _capi.check(o.lib.etainv_op_quick_gelu(_capi.ptr(f), _capi.ptr(f), f.numel(), o.code, o.st()))
+            x = o.gemm(f, *l["fc2"], residual=x)
+        return x.reshape(b, n, d)
+
+
+def clip_geometry(state_dict):
+    """the sizes of a transformers `CLIPModel` state dict, read from its tensor shapes"""
+    sd = state_dict
+    w = sd["vision_model.embeddings.patch_embedding.weight"]
+    g2 = sd["vision_model.embeddings.position_embedding.weight"].shape[0] - 1
+    count = lambda pre: len({k.split(".")[3] for k in sd if k.startswith(pre + "encoder.layers.")})
+    tok = sd["text_model.embeddings.token_embedding.weight"]
+    return {"width": w.shape[0], "layers": count("vision_model."), "patch": w.shape[-1], "image": math.isqrt(g2) * w.shape[-1],
+            "proj": sd["visual_projection.weight"].shape[0], "text_width": tok.shape[1], "text_layers": count("text_model."), "vocab": tok.shape[0]}
+
+
+class NativeCLIP:
+    """The two towers of a CLIP model and their projections: unit image and text embeddings (reference metrics/clip_similarity.py:191-221:
+    `model.encode_image` / `model.encode_text` divided by their norm)."""
+
+    def __init__(self, state_dict=None, compute_dtype=torch.float16, seed=0, width=768, layers=12, patch=16, image=224, proj=512, text_width=512,
+                 text_layers=12, vocab=49408):
+        if state_dict is not None:
+            gm = clip_geometry(state_dict)
+            width, layers, patch, image, proj = gm["width"], gm["layers"], gm["patch"], gm["image"], gm["proj"]
+            text_width, text_layers, vocab = gm["text_width"], gm["text_layers"], gm["vocab"]
+        self.cd, self.proj, self.patch, self.image, self.vocab = compute_dtype, proj, patch, image, vocab
+        self.vision = NativeCLIPVision(state_dict, compute_dtype, seed, layers=layers, d=width, patch=patch, image=image)
+        self.text = NativeCLIPText(state_dict, compute_dtype, seed, layers=text_layers, d=text_width, heads=text_width // 64, vocab=vocab)
+        get = lambda name, shape: state_dict[name].float() if state_dict is not None else synthetic_clip_tensor(name, shape, seed)
+        self.visual_projection = _dev(get("visual_projection.weight", (proj, width)), torch.float32)
+        self.text_projection = _dev(get("text_projection.weight", (proj, text_width)), torch.float32)
+
+    def _head(self, x, index, ln, w):
+        b, n, d = x.shape
+        out = torch.empty(b, self.proj, dtype=torch.float32, device="cuda")
+        lib = self.vision.ops.lib
+        _capi.check(lib.etainv_clip_embed_head(_capi.ptr(x), _capi.dtype_code(x.dtype), _capi.ptr(index), b, n, d, _capi.ptr(ln[0]) if ln else None,
+                                               _capi.ptr(ln[1]) if ln else None, 1e-5, _capi.ptr(w), _capi.F32, self.proj, _capi.ptr(out),
+                                               _capi.stream_ptr()))
+        return out
+
+    def image_features(self, rows, b):
+        """patch rows of b images -> unit embeddings (b, proj) fp32"""
+        return self._head(self.vision(rows, b).contiguous(), None, self.vision.post_ln, self.visual_projection)
+
+    def text_features(self, input_ids):
+        """(B, 77) int64 -> unit embeddings (B, proj) fp32, pooled at argmax(ids) (the end-of-text token: OpenAI's rule).  The text tower's
+        output is already final-LayerNormed: the head applies none."""
+        if int(input_ids.max()) >= self.vocab or int(input_ids.min()) < 0:      # (on the host when the ids are there: no device synchronisation)
+            raise ValueError(f"token id outside the vocabulary of {self.vocab} entries")
+        ids = input_ids.to(device="cuda", dtype=torch.int64)
+        hidden = self.text(ids)[0].contiguous()
+        return self._head(hidden, ids.argmax(-1).to(torch.int32).contiguous(), None, self.text_projection)

@@ -74,3 +74,103 @@ def load_component(path, sub) -> dict:
                 sd[k] = v
             return sd
     raise FileNotFoundError(f"no safetensors under {root}")
+
+
+# ---- CLIP (the metrics' model): transformers `CLIPModel` state-dict names throughout
+def synthetic_clip_tensor(name: str, shape, seed: int = 0) -> torch.Tensor:
+    """Synthetic value of one CLIP parameter: token / position / class embeddings 0.5 N(0, 1) (the rule of NativeCLIPText), everything else
+    `synthetic_tensor`"""
+    if "embedding" in name and "patch_embedding" not in name:
+        g = torch.Generator().manual_seed((zlib.crc32(name.encode()) + 1000003 * seed) & 0x7FFFFFFF)
+        return 0.5 * torch.randn(tuple(int(s) for s in shape), generator=g)
+    return synthetic_tensor("clip." + name, shape, seed)
+
+
+def synthetic_clip_state_dict(width=768, layers=12, patch=16, image=224, proj=512, text_width=512, text_layers=12, vocab=49408, seed=0) -> dict:
+    """every parameter the CLIP towers read, synthetic: what NativeCLIP builds without a state dict, as a state dict (the CPU path of the metrics
+    runs on the same values)"""
+    shapes = {"vision_model.embeddings.class_embedding": (width,),
+              "vision_model.embeddings.patch_embedding.weight": (width, 3, patch, patch),
+              "vision_model.embeddings.position_embedding.weight": ((image // patch) ** 2 + 1, width),
+              "text_model.embeddings.token_embedding.weight": (vocab, text_width),
+              "text_model.embeddings.position_embedding.weight": (77, text_width),
+              "visual_projection.weight": (proj, width), "text_projection.weight": (proj, text_width)}
+    for ln, d in (("vision_model.pre_layrnorm", width), ("vision_model.post_layernorm", width), ("text_model.final_layer_norm", text_width)):
+        shapes[ln + ".weight"] = shapes[ln + ".bias"] = (d,)
+    for pre, d, n in (("vision_model.", width, layers), ("text_model.", text_width, text_layers)):
+        for i in range(n):
+            p = f"{pre}encoder.layers.{i}."
+            for lin, (o, k) in {"self_attn.q_proj": (d, d), "self_attn.k_proj": (d, d), "self_attn.v_proj": (d, d), "self_attn.out_proj": (d, d),
+                                "mlp.fc1": (4 * d, d), "mlp.fc2": (d, 4 * d)}.items():
+                shapes[p + lin + ".weight"], shapes[p + lin + ".bias"] = (o, k), (o,)
+            for ln in ("layer_norm1", "layer_norm2"):
+                shapes[p + ln + ".weight"] = shapes[p + ln + ".bias"] = (d,)
+    return {name: synthetic_clip_tensor(name, shape, seed) for name, shape in shapes.items()}
+
+
+_OPENAI_BLOCK = {"ln_1": "layer_norm1", "ln_2": "layer_norm2", "attn.out_proj": "self_attn.out_proj", "mlp.c_fc": "mlp.fc1", "mlp.c_proj": "mlp.fc2"}
+_OPENAI_TOP = {"visual.conv1.weight": "vision_model.embeddings.patch_embedding.weight",
+               "visual.class_embedding": "vision_model.embeddings.class_embedding",
+               "visual.positional_embedding": "vision_model.embeddings.position_embedding.weight",
+               "visual.ln_pre.weight": "vision_model.pre_layrnorm.weight", "visual.ln_pre.bias": "vision_model.pre_layrnorm.bias",
+               "visual.ln_post.weight": "vision_model.post_layernorm.weight", "visual.ln_post.bias": "vision_model.post_layernorm.bias",
+               "token_embedding.weight": "text_model.embeddings.token_embedding.weight",
+               "positional_embedding": "text_model.embeddings.position_embedding.weight",
+               "ln_final.weight": "text_model.final_layer_norm.weight", "ln_final.bias": "text_model.final_layer_norm.bias",
+               "logit_scale": "logit_scale"}
+
+
+def openai_clip_to_transformers(sd: dict) -> dict:
+    """An OpenAI `clip` state dict under transformers' `CLIPModel` names: `attn.in_proj_*` split into q / k / v, the embeddings and norms
+    renamed, `visual.proj` and `text_projection` transposed (OpenAI multiplies from the right)."""
+    out = {}
+    for k, v in sd.items():
+        v = v.detach()
+        if k in _OPENAI_TOP:
+            out[_OPENAI_TOP[k]] = v
+        elif k == "visual.proj":
+            out["visual_projection.weight"] = v.t().contiguous()
+        elif k == "text_projection":
+            out["text_projection.weight"] = v.t().contiguous()
+        elif ".resblocks." in k:
+            head, rest = k.split(".resblocks.")
+            n, rest = rest.split(".", 1)
+            p = ("vision_model." if head == "visual.transformer" else "text_model.") + f"encoder.layers.{n}."
+            if rest.startswith("attn.in_proj_"):
+                kind = rest[len("attn.in_proj_"):]
+                for name, part in zip(("q_proj", "k_proj", "v_proj"), v.chunk(3, dim=0)):
+                    out[p + f"self_attn.{name}.{kind}"] = part.contiguous()
+            else:
+                mod, kind = rest.rsplit(".", 1)
+                out[p + _OPENAI_BLOCK[mod] + "." + kind] = v
+        elif k in ("input_resolution", "context_length", "vocab_size"):
+            continue                                                   # sizes the TorchScript archive carries as tensors
+        else:
+            raise KeyError(f"unexpected key in an OpenAI CLIP state dict: {k}")
+    return out
+
+
+def load_clip_state_dict(path) -> dict:
+    """The CLIP state dict at `path` (or the dict given) under transformers' `CLIPModel` names, fp32.  Accepted: a transformers `CLIPModel`
+    state dict (.safetensors or a torch file) and an OpenAI `clip` checkpoint -- the TorchScript archive `clip.load` caches or a plain state
+    dict -- which is renamed.  The geometry is read from the tensor shapes (nets.clip_geometry)."""
+    if isinstance(path, dict):
+        sd = path
+    elif str(path).endswith(".safetensors"):
+        from safetensors.torch import load_file
+        sd = load_file(str(path))
+    else:
+        try:
+            import warnings
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", DeprecationWarning)      # (the archive `clip.load` caches IS TorchScript)
+                sd = torch.jit.load(str(path), map_location="cpu").state_dict()
+        except RuntimeError:
+            sd = torch.load(str(path), map_location="cpu", weights_only=True)
+        if "state_dict" in sd:
+            sd = sd["state_dict"]
+    if "visual.conv1.weight" in sd:
+        sd = openai_clip_to_transformers(sd)
+    if "vision_model.embeddings.patch_embedding.weight" not in sd or "text_projection.weight" not in sd:
+        raise ValueError("not a CLIP state dict with a ViT image tower: vision_model.embeddings.patch_embedding.weight / text_projection.weight missing")
+    return {k: v.float() for k, v in sd.items() if torch.is_tensor(v) and v.is_floating_point()}

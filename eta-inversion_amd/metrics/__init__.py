@@ -1,9 +1,12 @@
-"""Image metrics of saved edits (reference metrics/): `EditMetric` over the metric classes, and `image_metrics`, the batched call they sit on."""
+"""Image metrics of saved edits (reference metrics/): `EditMetric` over the metric classes, and `image_metrics` / `clip_scores`, the batched calls they sit
+on."""
 from .base import BaseMetric, SimpleMetric
+from .clip_similarity import CLIPAccuracy, CLIPSimilarity, ClipModel, clip_scores
 from .edit_metric import EditMetric
 from .functional import NAMES, image_metrics
 from .metrics import MSEMetric, PSNRMetric
 from .msssim import MSSSIM
 from .ssim import SSIM
 
-__all__ = ["BaseMetric", "SimpleMetric", "EditMetric", "MSEMetric", "PSNRMetric", "SSIM", "MSSSIM", "image_metrics", "NAMES"]
+__all__ = ["BaseMetric", "SimpleMetric", "EditMetric", "MSEMetric", "PSNRMetric", "SSIM", "MSSSIM", "image_metrics", "NAMES", "CLIPSimilarity", "CLIPAccuracy",
+           "ClipModel", "clip_scores"]

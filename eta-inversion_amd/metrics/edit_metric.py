@@ -1,5 +1,6 @@
-"""One interface over the editing metrics (reference metrics/edit_metric.py:16-122).  Built: the four that need no pretrained network.  The CLIP,
-DINO-ViT and LPIPS families stay listed and are refused by name."""
+"""One interface over the editing metrics (reference metrics/edit_metric.py:16-122).  Built: the four that need no pretrained network, and -- only
+when weights are handed over with `clip_weights=` -- the four CLIP metrics that need no captioner.  Everything else stays listed and is refused by
+name."""
 from typing import Dict, List, Optional, Tuple, Union
 
 import numpy as np
@@ -11,15 +12,33 @@ from .msssim import MSSSIM
 from .ssim import SSIM
 
 _BUILT = {"ssim": SSIM, "msssim": MSSSIM, "mse": MSEMetric, "psnr": PSNRMetric}
+# built when `clip_weights=` is given: name -> (class name in .clip_similarity, its `metric`)
+_CLIP = {"clip_text_img": ("CLIPSimilarity", "text_img"), "clip_img_img": ("CLIPSimilarity", "img_img"),
+         "clip_textdir_imgdir": ("CLIPSimilarity", "textdir_imgdir"), "clip_text_img_acc": ("CLIPAccuracy", "text_img")}
+_CLIP_BLIP = ("clip_text_text", "clip_text_text_acc")
 _NAMES = ["clip_text_img", "clip_img_img", "clip_text_text", "clip_textdir_imgdir", "clip_text_img_acc", "clip_text_text_acc", "dinovitstruct",
           "dinovitstruct_v2", "lpips", "bglpips", "ssim", "msssim", "mse", "psnr"]
 
 
 class EditMetric(SimpleMetric):
     def __init__(self, name: str, input_range: Tuple[int, int] = (-1, 1), device: Optional[str] = None, **kwargs) -> None:
-        """`name`: one of get_available_metrics()"""
+        """`name`: one of get_available_metrics().  `clip_weights` (a path, a state dict, a loaded `ClipModel` or "synthetic"): builds the CLIP
+        metrics; `clip_templates`, `clip_model`: their caption templates and, for synthetic weights, the geometry."""
         super().__init__(input_range, device)
         self.metric_name = name
+        clip_weights = kwargs.pop("clip_weights", None)
+        clip_templates, clip_model = kwargs.pop("clip_templates", None), kwargs.pop("clip_model", "ViT-B/16")
+        self.is_clip = clip_weights is not None and name in _CLIP
+        if clip_weights is not None and name in _CLIP_BLIP:
+            raise NotImplementedError(f"metric '{name}' is not built: it needs a BLIP captioner (reference metrics/clip_similarity.py:128-157) besides "
+                                      f"the CLIP weights")
+        if self.is_clip:
+            from . import clip_similarity
+            cls, metric = _CLIP[name]
+            own = {} if isinstance(clip_weights, clip_similarity.ClipModel) else {"templates": clip_templates}
+            self.metric = getattr(clip_similarity, cls)(input_range=input_range, device=device, metric=metric, clip_model=clip_model,
+                                                        use_imagenet_templates=own.get("templates") is not None, weights=clip_weights, **own, **kwargs)
+            return
         if name not in _BUILT:
             raise NotImplementedError(f"metric '{name}' is not built: built are {', '.join(_BUILT)}; the others ({', '.join(n for n in _NAMES if n not in _BUILT)}, "
                                       f"nslpips) need pretrained CLIP / DINO / LPIPS weights")
@@ -37,8 +56,11 @@ class EditMetric(SimpleMetric):
     def update(self, source_image: torch.Tensor, edit_image: torch.Tensor, source_prompt: str, target_prompt: str, edit_word: str,
                mask: Optional[torch.Tensor] = None) -> float:
         """record one example: `source_image` the input image, `edit_image` the edited output.  The four built metrics take
-        (edit_image, source_image); prompts, edit word and mask are what the unbuilt ones take."""
-        loss = self.metric.update(edit_image, source_image)
+        (edit_image, source_image), the CLIP metrics the images and the prompts; edit word and mask are what the unbuilt ones take."""
+        if self.is_clip:                                         # by keyword, reference edit_metric.py:102-105
+            loss = self.metric.update(source_image=source_image, target_image=edit_image, source_prompt=source_prompt, target_prompt=target_prompt)
+        else:
+            loss = self.metric.update(edit_image, source_image)
         if isinstance(loss, torch.Tensor):
             loss = loss.item()
         elif isinstance(loss, np.ndarray):

@@ -201,6 +201,42 @@ int64_t etainv_image_metrics_workspace_bytes(int b, int h, int w, int mask);
 int etainv_image_metrics(const float* pred, const float* target, int b, int h, int w, float lo, float hi, int mask, float* out,
                          void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- CLIP metrics (reference metrics/clip_similarity.py): image preprocessing, the ViT's attention, the embedding head and the scores.  The
+ * towers' GEMMs, LayerNorms and quick-GELU are the etainv_op_* entry points further down.
+ *
+ * etainv_clip_preprocess: torch_to_pil (clip_similarity.py:223-239) and clip's transform (:201) for b square images in one launch.
+ *   x [b][3][s][s] fp32 in (lo, hi) -> (x - lo) / (hi - lo), * 255, clamped to [0, 255] and TRUNCATED to a byte -> Pillow's bicubic resize s -> r
+ *   on bytes (horizontal pass into bytes, then the vertical pass) -> / 255, - mean, / std (the published constants; float64, rounded once) -> the ViT's patch
+ *   rows rows_out [b (r / p)^2][Kp] in `dtype`: element k = c p^2 + py p + px (patch_embedding.weight.reshape(d, 3 p^2)), Kp = 3 p^2 rounded up
+ *   to 64, zero from 3 p^2 on.  u8_out (optional): the resized bytes [b][3][r][r].
+ *   The resampling is integer arithmetic on the caller's tables, built in float64 as Pillow builds them: bounds_* [r][2] = (first tap, taps),
+ *   coef_* [r][ksize_*] = the normalised a = -0.5 bicubic weights as int(w 2^22 +- 0.5); a byte is clip8((2^21 + sum w px) >> 22).  s == r:
+ *   one tap of weight 2^22 (Pillow does not resample).  max_rows: the most input rows a band of p output rows spans; max_rows (s + r) bytes of
+ *   LDS must fit in 65536.  Table values are clamped where they are used: a wrong table gives wrong pixels, never an access out of bounds.
+ *   Refused: a null pointer other than u8_out, p outside {14, 16, 32}, r not a multiple of p, a band that does not fit.
+ * etainv_clip_assemble_tokens: out [b][1 + g2][d] = (cls | patches [b][g2][d]) + pos [1 + g2][d]  (the ViT's embeddings module).
+ * etainv_op_vit_attention: softmax(q k^T / 8) v without a mask, qkv [b][n][3 heads 64] -> out [b][n][heads 64] (the layout of
+ *   etainv_op_causal_attention), any n >= 1; rows >= n are never read.  16-bit: MFMA flash kernel, fp32 online softmax, P rounded to the operand
+ *   type.  fp32: FMA twin.  Refused: head_dim != 64, a null or not 16-byte aligned pointer.
+ * etainv_clip_embed_head: model.encode_image / encode_text's last step and the division by the norm (clip_similarity.py:204-205, :119-120).
+ *   Row i of x [b][n][d] (x_dtype) at token index[i] (null: token 0) -> LayerNorm(gamma, beta, eps) when gamma is given -> proj [p][d]
+ *   (w_dtype, no bias) -> divided by its L2 norm -> out fp32 [b][p].  fp32 accumulation in a fixed order; a row's result does not depend on b.
+ * etainv_clip_similarity: the dot products of CLIPSimilarity.forward (:257-273) and the comparison of CLIPAccuracy.forward (:317-321) for b
+ *   pairs.  img_* [b][p], txt_* [b][t][p] unit embeddings; a prompt's t embeddings are averaged and renormalised (:118-125).  mode 0 text_img =
+ *   <img_tgt, txt_tgt>; 1 img_img = <img_src, img_tgt>; 2 textdir_imgdir = <img_tgt - img_src, txt_tgt - txt_src> (differences not
+ *   renormalised, :263-265); 3 text_img_acc = 1 if <img_tgt, txt_tgt> > <img_tgt, txt_src> else 0.  out fp32 [b]; mode 4: all four of every
+ *   pair in one launch, out fp32 [b][4] in that order, each value bit-identical to its own mode's.  float64 arithmetic, fixed
+ *   order.  Refused: an unknown mode, t < 1, a null pointer the mode needs. */
+int etainv_clip_preprocess(const float* x, int b, int s, int r, int p, float lo, float hi, const int32_t* bounds_h, const int32_t* coef_h,
+                           int ksize_h, const int32_t* bounds_v, const int32_t* coef_v, int ksize_v, int max_rows, void* rows_out,
+                           uint8_t* u8_out, int dtype, void* stream);
+int etainv_clip_assemble_tokens(const void* patches, const void* cls, const void* pos, void* out, int b, int g2, int d, int dtype, void* stream);
+int etainv_op_vit_attention(const void* qkv, void* out, int b, int n, int heads, int d, int dtype, void* stream);
+int etainv_clip_embed_head(const void* x, int x_dtype, const int32_t* index, int b, int n, int d, const float* gamma, const float* beta, float eps,
+                           const void* proj, int w_dtype, int p, float* out, void* stream);
+int etainv_clip_similarity(const float* img_src, const float* img_tgt, const float* txt_src, const float* txt_tgt, int b, int t, int p, int mode,
+                           float* out, void* stream);
+
 /* ---------------------------------------------------------------- engine */
 typedef struct etainv_engine etainv_engine_t;
 
