@@ -4,6 +4,7 @@
     python compute_metrics.py --data_path data/eval/PIE-Bench_v1 --output result/pie_etainv_ptp [--metric mse psnr ssim msssim]
                               [--batch 32] [--device cuda|cpu] [--size 512] [--limit N] [--categories 1_change_object ...]
                               [--clip_weights PATH|synthetic] [--clip_tokenizer DIR] [--clip_templates FILE] [--clip_model ViT-B/16]
+                              [--dino_weights PATH|synthetic] [--dino_model dino_vitb8]
 
 Reads the layout eval.py writes, `<output>/imgs/{i:04d}_{source}_{target}.png`, next to the data set's source images.  Kept from the reference:
 one `<output>/metrics/<name>.yaml` per metric, {name, mean, results: [{value, file}]}; a metric whose yaml exists is skipped (the file is
@@ -13,7 +14,8 @@ samples are processed --batch at a time, all wanted metrics of a batch in one `i
 that are built (EditMetric refuses the others by name).  The CLIP metrics (clip_text_img, clip_img_img, clip_textdir_imgdir, clip_text_img_acc) are
 computed only when --clip_weights hands their weights over (a transformers CLIPModel state dict or an OpenAI clip checkpoint; "synthetic" with
 --clip_model for dry runs): the data set's prompts go with every pair into one `clip_scores` call per batch.  --clip_templates FILE: one caption
-template per line, each with a {} for the prompt."""
+template per line, each with a {} for the prompt.  dinovitstruct is computed only when --dino_weights hands DINO's checkpoint over ("synthetic" with
+--dino_model for dry runs): one `dino_structure` call per batch."""
 import argparse
 import sys
 from pathlib import Path
@@ -45,6 +47,9 @@ def parse_args(argv=None):
     ap.add_argument("--clip_model", default="ViT-B/16", help="geometry of --clip_weights synthetic")
     ap.add_argument("--clip_tokenizer", default=None, help="directory with CLIP's vocab.json and merges.txt (default: ETAINV_SD_PATH/tokenizer); "
                     "trained weights are refused without one")
+    ap.add_argument("--dino_weights", default=None, help="DINO ViT weights (the published checkpoint, a state dict file, or 'synthetic'); without it "
+                    "dinovitstruct is refused")
+    ap.add_argument("--dino_model", default="dino_vitb8", help="the metric's model name; geometry of --dino_weights synthetic")
     return ap.parse_args(argv)
 
 
@@ -52,7 +57,7 @@ def _claim(metric_dir: Path, metrics):
     """the metrics whose yaml this run creates (exclusive create, reference :44-51), with their files"""
     mine = []
     for m in metrics:
-        f = metric_dir / f"{m}.yaml"
+        f = metric_dir / f"{m.metric_name}.yaml"               # (the metric's name, not its repr: dinovitstruct prints its model's name)
         try:
             open(f, "x").close()
         except FileExistsError:
@@ -62,24 +67,28 @@ def _claim(metric_dir: Path, metrics):
     return mine
 
 
-def _compute(names, edits, sources, prompts, clip):
-    """{name: tensor [B]} of one batch: the image metrics in one `image_metrics` call, the CLIP metrics in one `clip_scores` call"""
+def _compute(names, edits, sources, prompts, clip, dino=None):
+    """{name: tensor [B]} of one batch: the image metrics in one `image_metrics` call, the CLIP metrics in one `clip_scores` call, dinovitstruct
+    in one `dino_structure` call"""
     out = {}
     image = [n for n in names if n in IMAGE_NAMES]
     if image:
         out.update(image_metrics(torch.cat(edits), torch.cat(sources), (-1, 1), image))
-    other = [n for n in names if n not in IMAGE_NAMES]
+    if "dinovitstruct" in names:
+        from metrics import dino_structure
+        out["dinovitstruct"] = dino_structure(torch.cat(edits), torch.cat(sources), dino, (-1, 1))
+    other = [n for n in names if n not in IMAGE_NAMES and n != "dinovitstruct"]
     if other:
         from metrics import clip_scores
         out.update(clip_scores(torch.cat(edits), torch.cat(sources), [p[0] for p in prompts], [p[1] for p in prompts], other, clip, (-1, 1)))
     return out
 
 
-def _values(names, edits, sources, prompts=None, clip=None):
+def _values(names, edits, sources, prompts=None, clip=None, dino=None):
     """{name: [float per pair]}: one call for the batch; if it raises, pair by pair and metric by metric, nan where that raises"""
     prompts = prompts or [("", "")] * len(edits)
     try:
-        out = _compute(names, edits, sources, prompts, clip)
+        out = _compute(names, edits, sources, prompts, clip, dino)
         return {n: [float(v) for v in out[n].cpu()] for n in names}
     except Exception:
         pass
@@ -87,7 +96,7 @@ def _values(names, edits, sources, prompts=None, clip=None):
     for e, s, p in zip(edits, sources, prompts):
         for n in names:
             try:
-                vals[n].append(float(_compute((n,), [e], [s], [p], clip)[n][0]))
+                vals[n].append(float(_compute((n,), [e], [s], [p], clip, dino)[n][0]))
             except Exception as exc:
                 print(f"{n}: nan because of {exc}")
                 vals[n].append(float("nan"))
@@ -108,14 +117,19 @@ def main(argv=None):
         clip = ClipModel(a.clip_weights, device, a.clip_model, templates=templates, tokenizer=a.clip_tokenizer)
         if any(m != "clip_img_img" for m in a.metric if m.startswith("clip_")):
             clip.tokenize(["a"])                                 # trained weights without a CLIP tokenizer: refused here, before any yaml is claimed
-    metrics = [EditMetric(m, input_range=(-1, 1), device=device, **({"clip_weights": clip} if clip is not None and m.startswith("clip_") else {}))
-               for m in (a.metric or EditMetric.get_built_metrics())]
+    dino = None
+    if a.dino_weights is not None and "dinovitstruct" in (a.metric or []):
+        from metrics import DinoModel
+        dino = DinoModel(a.dino_weights, device, a.dino_model)
+    own = lambda m: ({"clip_weights": clip} if clip is not None and m.startswith("clip_") else
+                     {"dino_weights": dino, "dino_model": a.dino_model} if dino is not None and m == "dinovitstruct" else {})
+    metrics = [EditMetric(m, input_range=(-1, 1), device=device, **own(m)) for m in (a.metric or EditMetric.get_built_metrics())]
     metric_dir = Path(a.output) / "metrics"
     metric_dir.mkdir(parents=True, exist_ok=True)
     mine = _claim(metric_dir, metrics)
     if not mine:
         return
-    names = [str(m) for m, _ in mine]
+    names = [m.metric_name for m, _ in mine]
     from modules.models import StablePreprocess
     preproc = StablePreprocess(device, size=a.size, center_crop=True)
     data = PieBenchData(a.data_path, skip_img_load=True, limit=a.limit, categories=a.categories)
@@ -124,7 +138,7 @@ def main(argv=None):
     def flush(stems, edits, sources, prompts):
         if not stems:
             return
-        vals = _values(names, edits, sources, prompts, clip)
+        vals = _values(names, edits, sources, prompts, clip, dino)
         for (m, _), n in zip(mine, names):
             m.metric.losses.extend(vals[n])                      # what EditMetric.update records, for the whole batch
             results[n].extend({"value": v, "file": stem} for v, stem in zip(vals[n], stems))

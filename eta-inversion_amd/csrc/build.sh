@@ -3,7 +3,7 @@
 set -e
 HERE="$(cd "$(dirname "$0")" && pwd)"
 OUT="$HERE/../etainv/lib"
-OBJ="$HERE/obj"; LIBNAME=libetainv_hip.so; SRCS="step_kernels ddpm regularize proximal metrics clip igemm norm attention misc maps aux_nets f32path ppgemm ppconv"
+OBJ="$HERE/obj"; LIBNAME=libetainv_hip.so; SRCS="step_kernels ddpm regularize proximal metrics clip dino igemm norm attention misc maps aux_nets f32path ppgemm ppconv"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result"
 mkdir -p "$OUT" "$OBJ"
 pids=()
@@ -32,8 +32,11 @@ echo "built $OUT/$LIBNAME"
 # proximal.hip keeps up to 32 values per thread in registers through five passes.  Expected, prox_guidance_kernel<Q> at 1024 threads:
 # <4> 46 VGPRs, <32> 110 VGPRs, <0> 42 VGPRs; no spill and no scratch in any of the three; 17,424 B of LDS each.
 # metrics.hip: metrics_level_kernel<float / double> at 256 threads: 114 VGPRs, no scratch, 44,456 B of LDS (three blocks per CU).
+# dino.hip at 256 threads: dino_selfsim_kernel<f16 / bf16> 58 VGPRs + 32 AGPRs (the two Gram tiles' accumulators), no scratch, 36,896 B of LDS
+# (four 64 x 72 slabs: four blocks per CU); dino_selfsim_f32_kernel 86 VGPRs, no scratch, 33,824 B; dino_preprocess_kernel 19-21 VGPRs, no
+# scratch, max_rows * R * 4 B of dynamic LDS (18,816 B for 512 -> 224 at patch 8); the row-norm, GELU and finalize kernels 8-12 VGPRs, no LDS.
 if [ "${RESOURCES:-0}" = "1" ]; then
-  for f in regularize proximal metrics; do
+  for f in regularize proximal metrics dino; do
     hipcc $FLAGS --cuda-device-only -Rpass-analysis=kernel-resource-usage -c "$HERE/$f.hip" -o /dev/null 2>&1 | grep -E "Function Name|VGPRs|ScratchSize" || true
   done
 fi

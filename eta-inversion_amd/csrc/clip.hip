@@ -123,18 +123,6 @@ constexpr int VA_D = 64, VA_BQ = 64, VA_BK = 32;
 constexpr int VA_KS = VA_D + 8;      // K tile row stride in elements (144 B: 16-byte aligned rows)
 constexpr int VA_VS = VA_BK + 8;     // V^T tile row stride in elements (80 B: 8-byte aligned rows)
 
-template <typename T> struct ClipFrag;
-template <> struct ClipFrag<f16> {
-  typedef f16x8 v8;
-  typedef f16x4 v4;
-  static __device__ __forceinline__ f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
-template <> struct ClipFrag<bf16> {
-  typedef bf16x8 v8;
-  typedef bf16x4 v4;
-  static __device__ __forceinline__ f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
-
 template <typename T>
 __global__ void __launch_bounds__(CLIP_THREADS) vit_attention_kernel(const T* __restrict__ qkv, T* __restrict__ out, int n, int heads, float scale_log2) {
   typedef typename ClipFrag<T>::v8 v8;

@@ -238,6 +238,20 @@ int launch_prox_guidance(const float* eps_u, const float* eps_c, float g, int mo
 int launch_image_metrics(const float* pred, const float* target, int b, int h, int w, float lo, float hi, int mask, float* out, void* workspace,
                          int64_t workspace_bytes, hipStream_t s);
 
+// ---- clip.hip, dino.hip: the 16x16x32 MFMA of either 16-bit operand type behind one name (A[row = lane & 15][k = 8 (lane >> 4) + j],
+// B[k][col = lane & 15], C[row = 4 (lane >> 4) + r][col = lane & 15])
+template <typename T> struct ClipFrag;
+template <> struct ClipFrag<f16> {
+  typedef f16x8 v8;
+  typedef f16x4 v4;
+  static __device__ __forceinline__ f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+};
+template <> struct ClipFrag<bf16> {
+  typedef bf16x8 v8;
+  typedef bf16x4 v4;
+  static __device__ __forceinline__ f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+};
+
 // ---- maps.hip
 int launch_word_maps(const float* maps_acc, int n_layers, int n_img_cap, int rows_per_img, int row_sel, int heads, int res, int L,
                      int n_img, const int32_t* tokens, int n_tok, int steps_done, float* out, int accumulate, float scale,

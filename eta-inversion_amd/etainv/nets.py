@@ -341,6 +341,92 @@ class NativeCLIPVision:
         return x.reshape(b, n, d)
 
 
+class NativeDinoVision:
+    """DINO's ViT (the names of its published checkpoints) up to the keys of its last block: patch-embedding GEMM WITH bias on the rows
+    etainv_dino_preprocess writes, class token + position embeddings, then the pre-LN blocks of NativeCLIPVision with LayerNorm eps 1e-6 and the
+    erf GELU (etainv_op_gelu_erf); no pre-LayerNorm and no final norm.  The last block runs only norm1 and the key third of its qkv GEMM (weight
+    rows d .. 2d-1 with their bias): `blocks[L-1].attn.qkv`'s output columns d .. 2d-1, which is what the reference's hook keeps
+    (dino_vit_structure.py:182-189).  heads = d / 64; any depth L >= 1 (the reference asserts L = 12: its models have 12 blocks; the keys are
+    those of block L-1 here).  The geometry comes from the tensor shapes (dino_geometry)."""
+
+    def __init__(self, state_dict, compute_dtype=torch.float16):
+        gm = dino_geometry(state_dict)
+        d, patch, layers = gm["width"], gm["patch"], gm["layers"]
+        self.ops, self.cd, self.d, self.heads, self.patch, self.image, self.g2 = _Ops(compute_dtype), compute_dtype, d, d // 64, patch, gm["image"], gm["g2"]
+        f32 = torch.float32
+        g = lambda name, shape: self._get(state_dict, name, shape)
+        self.kp = 3 * patch * patch
+        self.patch_w = _dev(g("patch_embed.proj.weight", (d, 3, patch, patch)).reshape(d, self.kp), compute_dtype)
+        self.patch_b = _dev(g("patch_embed.proj.bias", (d,)), f32)
+        self.cls = _dev(g("cls_token", (1, 1, d)).reshape(d), compute_dtype)
+        self.pos = _dev(g("pos_embed", (1, self.g2 + 1, d)).reshape(self.g2 + 1, d), compute_dtype)
+        lin = lambda name, o, k: (_dev(g(name + ".weight", (o, k)), compute_dtype), _dev(g(name + ".bias", (o,)), f32))
+        ln = lambda name: (_dev(g(name + ".weight", (d,)), f32), _dev(g(name + ".bias", (d,)), f32))
+        self.layers = []
+        for i in range(layers - 1):
+            p = f"blocks.{i}."
+            self.layers.append({"ln1": ln(p + "norm1"), "qkv": lin(p + "attn.qkv", 3 * d, d), "out": lin(p + "attn.proj", d, d), "ln2": ln(p + "norm2"),
+                                "fc1": lin(p + "mlp.fc1", 4 * d, d), "fc2": lin(p + "mlp.fc2", d, 4 * d)})
+        p = f"blocks.{layers - 1}."
+        self.last_ln = ln(p + "norm1")
+        self.key_w = _dev(g(p + "attn.qkv.weight", (3 * d, d))[d:2 * d], compute_dtype)
+        self.key_b = _dev(g(p + "attn.qkv.bias", (3 * d,))[d:2 * d], f32)
+
+    @staticmethod
+    def _get(sd, name, shape):
+        if name not in sd:
+            raise ValueError(f"DINO state dict: {name} missing")
+        t = sd[name].float()
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"DINO state dict: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+        return t
+
+    def __call__(self, rows, b):
+        """patch rows [b g^2][3 p^2] (compute dtype, from etainv_dino_preprocess) -> the last block's keys [b][1 + g^2][d] (compute dtype)"""
+        o, d, n = self.ops, self.d, self.g2 + 1
+        assert rows.shape == (b * self.g2, self.kp) and rows.dtype == self.cd, (rows.shape, rows.dtype)
+        pe = o.gemm(rows, self.patch_w, self.patch_b)
+        x = torch.empty(b * n, d, dtype=self.cd, device="cuda")
+        _capi.check(o.lib.etainv_clip_assemble_tokens(_capi.ptr(pe), _capi.ptr(self.cls), _capi.ptr(self.pos), _capi.ptr(x), b, self.g2, d, o.code, o.st()))
+        for l in self.layers:
+            qkv = o.gemm(o.ln(x, *l["ln1"], eps=1e-6), *l["qkv"])
+            att = torch.empty(b * n, d, dtype=self.cd, device="cuda")
+            _capi.check(o.lib.etainv_op_vit_attention(_capi.ptr(qkv), _capi.ptr(att), b, n, self.heads, 64, o.code, o.st()))
+            x = o.gemm(att, *l["out"], residual=x)
+            f = o.gemm(o.ln(x, *l["ln2"], eps=1e-6), *l["fc1"])
+            _capi.check(o.lib.etainv_op_gelu_erf(_capi.ptr(f), _capi.ptr(f), f.numel(), o.code, o.st()))
+            x = o.gemm(f, *l["fc2"], residual=x)
+        return o.gemm(o.ln(x, *self.last_ln, eps=1e-6), self.key_w, self.key_b).reshape(b, n, d)
+
+
+def dino_geometry(state_dict, image=None):
+    """the sizes of a DINO ViT state dict, read from its tensor shapes; refuses, with the reason, what the tower is not built for.  `image`: the
+    side the model runs at (None: 224, or the model's own side when its position table is smaller -- tiny models)"""
+    sd = state_dict
+    bad = sorted({part for k in sd for part in k.split(".") if part in ("ls1", "ls2", "gamma_1", "gamma_2", "register_tokens")})
+    if bad:
+        raise ValueError(f"a DINOv2 state dict ({', '.join(bad)}): LayerScale and register tokens are not built (dinovitstruct_v2)")
+    for k in ("patch_embed.proj.weight", "pos_embed", "cls_token"):
+        if k not in sd:
+            raise ValueError(f"not a DINO ViT state dict: {k} missing")
+    w, n_pos = sd["patch_embed.proj.weight"], sd["pos_embed"].shape[-2]
+    d, p = w.shape[0], w.shape[-1]
+    if d % 64:
+        raise ValueError(f"DINO tower: width {d} is not a multiple of 64 (heads of 64 channels)")
+    if p not in (8, 16) or w.shape[-2] != p:
+        raise ValueError(f"DINO tower: patch size {tuple(w.shape[-2:])} must be 8 x 8 or 16 x 16")
+    layers = len({k.split(".")[1] for k in sd if k.startswith("blocks.")})
+    if layers < 1:
+        raise ValueError("DINO tower: no blocks in the state dict")
+    own = math.isqrt(max(n_pos - 1, 0)) * p
+    if image is None:
+        image = 224 if n_pos == 1 + (224 // p) ** 2 else own
+    if n_pos != 1 + (image // p) ** 2 or image % p or image < p:
+        raise ValueError(f"DINO tower: pos_embed has {n_pos} rows, expected 1 + ({image} / {p})^2 = {1 + (image // p) ** 2} (the position embeddings are "
+                         f"not interpolated: the model runs at the image size it was trained at)")
+    return {"width": d, "patch": p, "layers": layers, "image": image, "g2": (image // p) ** 2}
+
+
 def clip_geometry(state_dict):
     """the sizes of a transformers `CLIPModel` state dict, read from its tensor shapes"""
     sd = state_dict

@@ -174,3 +174,56 @@ def load_clip_state_dict(path) -> dict:
     if "vision_model.embeddings.patch_embedding.weight" not in sd or "text_projection.weight" not in sd:
         raise ValueError("not a CLIP state dict with a ViT image tower: vision_model.embeddings.patch_embedding.weight / text_projection.weight missing")
     return {k: v.float() for k, v in sd.items() if torch.is_tensor(v) and v.is_floating_point()}
+
+
+# ---- DINO (the dinovitstruct metric's model): the names of DINO's published ViT checkpoints throughout
+_DINO_V2_KEYS = ("ls1", "ls2", "gamma_1", "gamma_2", "register_tokens", "mask_token")
+
+
+def synthetic_dino_state_dict(width=768, layers=12, patch=8, image=224, seed=0) -> dict:
+    """every parameter the DINO tower reads, synthetic: class token and position embeddings 0.5 N(0, 1), everything else `synthetic_tensor`"""
+    d = width
+    shapes = {"cls_token": (1, 1, d), "pos_embed": (1, (image // patch) ** 2 + 1, d), "patch_embed.proj.weight": (d, 3, patch, patch),
+              "patch_embed.proj.bias": (d,), "norm.weight": (d,), "norm.bias": (d,)}
+    for i in range(layers):
+        p = f"blocks.{i}."
+        for lin, (o, k) in {"attn.qkv": (3 * d, d), "attn.proj": (d, d), "mlp.fc1": (4 * d, d), "mlp.fc2": (d, 4 * d)}.items():
+            shapes[p + lin + ".weight"], shapes[p + lin + ".bias"] = (o, k), (o,)
+        for ln in ("norm1", "norm2"):
+            shapes[p + ln + ".weight"] = shapes[p + ln + ".bias"] = (d,)
+    out = {}
+    for name, shape in shapes.items():
+        if name in ("cls_token", "pos_embed"):
+            g = torch.Generator().manual_seed((zlib.crc32(("dino." + name).encode()) + 1000003 * seed) & 0x7FFFFFFF)
+            out[name] = 0.5 * torch.randn(shape, generator=g)
+        else:
+            out[name] = synthetic_tensor("dino." + name, shape, seed)
+    return out
+
+
+def load_dino_state_dict(path) -> dict:
+    """The DINO ViT state dict at `path` (or the dict given), fp32, under the names of DINO's published backbone checkpoints (`cls_token`,
+    `pos_embed`, `patch_embed.proj`, `blocks.N.*`).  A full training checkpoint is unwrapped (`teacher`, else `state_dict`) and the prefixes
+    `module.` and `backbone.` are stripped; the projection head's tensors are dropped.  DINOv2 state dicts (LayerScale, register tokens) are
+    refused: that model is `dinovitstruct_v2`, which is not built."""
+    sd = path if isinstance(path, dict) else torch.load(str(path), map_location="cpu", weights_only=True)
+    for wrap in ("teacher", "state_dict"):
+        if wrap in sd and isinstance(sd[wrap], dict):
+            sd = sd[wrap]
+            break
+    out = {}
+    for k, v in sd.items():
+        for pre in ("module.", "backbone."):
+            if k.startswith(pre):
+                k = k[len(pre):]
+        if k.startswith("head.") or not torch.is_tensor(v) or not v.is_floating_point():
+            continue
+        out[k] = v.detach().float()
+    bad = sorted({part for k in out for part in k.split(".") if part in _DINO_V2_KEYS})
+    if bad:
+        raise ValueError(f"a DINOv2 state dict ({', '.join(bad)}): dinovitstruct takes the DINO ViT checkpoints; dinovitstruct_v2 (patch 14, LayerScale, "
+                         f"interpolated position embeddings) is not built")
+    missing = [k for k in ("cls_token", "pos_embed", "patch_embed.proj.weight", "patch_embed.proj.bias", "blocks.0.attn.qkv.weight") if k not in out]
+    if missing:
+        raise ValueError(f"not a DINO ViT state dict: {', '.join(missing)} missing")
+    return out

@@ -1,6 +1,6 @@
-"""One interface over the editing metrics (reference metrics/edit_metric.py:16-122).  Built: the four that need no pretrained network, and -- only
-when weights are handed over with `clip_weights=` -- the four CLIP metrics that need no captioner.  Everything else stays listed and is refused by
-name."""
+"""One interface over the editing metrics (reference metrics/edit_metric.py:16-122).  Built: the four that need no pretrained network, -- only
+when weights are handed over with `clip_weights=` -- the four CLIP metrics that need no captioner, and -- only with `dino_weights=` -- dinovitstruct.
+Everything else stays listed and is refused by name."""
 from typing import Dict, List, Optional, Tuple, Union
 
 import numpy as np
@@ -23,12 +23,21 @@ _NAMES = ["clip_text_img", "clip_img_img", "clip_text_text", "clip_textdir_imgdi
 class EditMetric(SimpleMetric):
     def __init__(self, name: str, input_range: Tuple[int, int] = (-1, 1), device: Optional[str] = None, **kwargs) -> None:
         """`name`: one of get_available_metrics().  `clip_weights` (a path, a state dict, a loaded `ClipModel` or "synthetic"): builds the CLIP
-        metrics; `clip_templates`, `clip_model`: their caption templates and, for synthetic weights, the geometry."""
+        metrics; `clip_templates`, `clip_model`: their caption templates and, for synthetic weights, the geometry.  `dino_weights` (a path, a state
+        dict, a loaded `DinoModel` or "synthetic"): builds dinovitstruct; `dino_model`: its printed name and, for synthetic weights, the geometry."""
         super().__init__(input_range, device)
         self.metric_name = name
         clip_weights = kwargs.pop("clip_weights", None)
         clip_templates, clip_model = kwargs.pop("clip_templates", None), kwargs.pop("clip_model", "ViT-B/16")
+        dino_weights, dino_model = kwargs.pop("dino_weights", None), kwargs.pop("dino_model", "dino_vitb8")
         self.is_clip = clip_weights is not None and name in _CLIP
+        if dino_weights is not None and name == "dinovitstruct_v2":
+            raise NotImplementedError("metric 'dinovitstruct_v2' is not built: besides DINOv2 weights it needs a ViT with patch 14, LayerScale and "
+                                      "interpolated position embeddings (reference metrics/dino_vit_structure.py:33-34, :121-122)")
+        if dino_weights is not None and name == "dinovitstruct":
+            from .dino_vit_structure import DinoVitStructure
+            self.metric = DinoVitStructure(input_range=input_range, device=device, vit_model=dino_model, weights=dino_weights, **kwargs)
+            return
         if clip_weights is not None and name in _CLIP_BLIP:
             raise NotImplementedError(f"metric '{name}' is not built: it needs a BLIP captioner (reference metrics/clip_similarity.py:128-157) besides "
                                       f"the CLIP weights")
@@ -56,9 +65,12 @@ class EditMetric(SimpleMetric):
     def update(self, source_image: torch.Tensor, edit_image: torch.Tensor, source_prompt: str, target_prompt: str, edit_word: str,
                mask: Optional[torch.Tensor] = None) -> float:
         """record one example: `source_image` the input image, `edit_image` the edited output.  The four built metrics take
-        (edit_image, source_image), the CLIP metrics the images and the prompts; edit word and mask are what the unbuilt ones take."""
+        (edit_image, source_image), the CLIP metrics the images and the prompts, dinovitstruct (source_image, edit_image) as the reference
+        does (edit_metric.py:93); edit word and mask are what the unbuilt ones take."""
         if self.is_clip:                                         # by keyword, reference edit_metric.py:102-105
             loss = self.metric.update(source_image=source_image, target_image=edit_image, source_prompt=source_prompt, target_prompt=target_prompt)
+        elif self.metric_name == "dinovitstruct":
+            loss = self.metric.update(source_image, edit_image)
         else:
             loss = self.metric.update(edit_image, source_image)
         if isinstance(loss, torch.Tensor):

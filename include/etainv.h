@@ -237,6 +237,37 @@ int etainv_clip_embed_head(const void* x, int x_dtype, const int32_t* index, int
 int etainv_clip_similarity(const float* img_src, const float* img_tgt, const float* txt_src, const float* txt_tgt, int b, int t, int p, int mode,
                            float* out, void* stream);
 
+/* ---- dinovitstruct (reference metrics/dino_vit_structure.py): image preprocessing, the erf GELU of the DINO blocks and the fused key
+ * self-similarity distance.  The DINO ViT tower runs on etainv_op_gemm / etainv_op_layernorm, etainv_clip_assemble_tokens and etainv_op_vit_attention.
+ *
+ * etainv_dino_preprocess: SimpleMetric._normalize, Resize(224) on a float tensor and the ImageNet normalisation (dino_vit_structure.py:236-241)
+ *   for b square images in one launch.  x [b][3][s][s] fp32 in (lo, hi) -> (x - lo) / (hi - lo) -> the separable resize s -> r in fp32 (horizontal
+ *   pass, then vertical; one FMA per tap) -> (v - mean) / std with mean (0.485, 0.456, 0.406), std (0.229, 0.224, 0.225), in float64, rounded
+ *   once -> the ViT's patch rows rows_out [b (r / p)^2][3 p^2] in `dtype`: element k = c p^2 + py p + px (patch_embed.proj.weight.reshape(d, 3 p^2)).
+ *   Nothing is quantised to bytes.  The tables are the caller's, built in float64: bounds_* [r][2] = (first tap, taps), coef_* [r][ksize_*] fp32
+ *   weights that sum to 1 -- torch's antialiased bilinear weights, or the two taps of antialias=False.  max_rows: the most input rows a band of p
+ *   output rows spans; max_rows r 4 bytes of LDS must fit in 65536 (512 -> 224 at p = 8 needs 21 rows).  Table values are clamped where they are
+ *   used: a wrong table gives wrong pixels, never an access out of bounds.  Refused: a null or misaligned pointer, p outside {8, 16}, r not a
+ *   multiple of p, b above 65535, a band that does not fit.
+ * etainv_op_gelu_erf: out = x Phi(x), the exact GELU, element-wise (in place allowed); erf to 1.8e-7 (gelu_pair).
+ * etainv_dino_selfsim_mse: attn_cosine_sim (:15-20) of the source's and the edit's keys and F.mse_loss between the two (:262), for b pairs.
+ *   keys [2 b][n][ld] in `dtype` with d used columns per row: rows 0 .. b-1 the sources' keys, b .. 2 b-1 the edits'.  With
+ *   sim[i][j] = <k_i, k_j> / max(|k_i| |k_j|, eps) (the clamp is on the PRODUCT of the norms; a zero key gives 0),
+ *   scores_out[pair] = mean over all n^2 (i, j) of (sim_edit - sim_source)^2, float64.  norms_out (optional): the fp32 row norms [2 b][n].
+ *   Dots accumulate in fp32 (16-bit: MFMA over 64 x 64 tiles with j-tile >= i-tile, off-diagonal tiles counted twice; fp32: FMA twin), the
+ *   cosines are fp32, their difference, its square and every sum float64 in a fixed order without atomics: a pair's score does not depend on
+ *   b or on its position and is bit-identical from run to run.  Neither n x n matrix is written.  workspace: a device buffer of at least
+ *   etainv_dino_selfsim_workspace_bytes(b, n) bytes (-1: refused), 8-byte aligned; its contents mean nothing between calls.
+ *   Refused: a null pointer other than norms_out, keys not 16-byte aligned, d not a multiple of 64, ld < d or ld rows not whole 16-byte
+ *   vectors, eps <= 0, b above 32767, n above 16384, a workspace too small. */
+int etainv_dino_preprocess(const float* x, int b, int s, int r, int p, float lo, float hi, const int32_t* bounds_h, const float* coef_h,
+                           int ksize_h, const int32_t* bounds_v, const float* coef_v, int ksize_v, int max_rows, void* rows_out, int dtype,
+                           void* stream);
+int etainv_op_gelu_erf(const void* x, void* out, int64_t n, int dtype, void* stream);
+int64_t etainv_dino_selfsim_workspace_bytes(int b, int n);
+int etainv_dino_selfsim_mse(const void* keys, int b, int n, int d, int64_t ld, float eps, double* scores_out, float* norms_out, void* workspace,
+                            int64_t workspace_bytes, int dtype, void* stream);
+
 /* ---------------------------------------------------------------- engine */
 typedef struct etainv_engine etainv_engine_t;
 
