@@ -5,6 +5,7 @@
                               [--batch 32] [--device cuda|cpu] [--size 512] [--limit N] [--categories 1_change_object ...]
                               [--clip_weights PATH|synthetic] [--clip_tokenizer DIR] [--clip_templates FILE] [--clip_model ViT-B/16]
                               [--dino_weights PATH|synthetic] [--dino_model dino_vitb8]
+                              [--lpips_weights PATH[,PATH]|synthetic] [--lpips_net alex]
 
 Reads the layout eval.py writes, `<output>/imgs/{i:04d}_{source}_{target}.png`, next to the data set's source images.  Kept from the reference:
 one `<output>/metrics/<name>.yaml` per metric, {name, mean, results: [{value, file}]}; a metric whose yaml exists is skipped (the file is
@@ -15,7 +16,9 @@ that are built (EditMetric refuses the others by name).  The CLIP metrics (clip_
 computed only when --clip_weights hands their weights over (a transformers CLIPModel state dict or an OpenAI clip checkpoint; "synthetic" with
 --clip_model for dry runs): the data set's prompts go with every pair into one `clip_scores` call per batch.  --clip_templates FILE: one caption
 template per line, each with a {} for the prompt.  dinovitstruct is computed only when --dino_weights hands DINO's checkpoint over ("synthetic" with
---dino_model for dry runs): one `dino_structure` call per batch."""
+--dino_model for dry runs): one `dino_structure` call per batch.  lpips and bglpips are computed only when --lpips_weights hands the LPIPS AlexNet
+over (one file in lpips.LPIPS's state-dict form, or backbone,heads; "synthetic" for dry runs): one `lpips_distance` call per batch and per name,
+bglpips with the data set's foreground masks, which are 512 x 512: any other --size is refused for it."""
 import argparse
 import sys
 from pathlib import Path
@@ -50,6 +53,9 @@ def parse_args(argv=None):
     ap.add_argument("--dino_weights", default=None, help="DINO ViT weights (the published checkpoint, a state dict file, or 'synthetic'); without it "
                     "dinovitstruct is refused")
     ap.add_argument("--dino_model", default="dino_vitb8", help="the metric's model name; geometry of --dino_weights synthetic")
+    ap.add_argument("--lpips_weights", default=None, help="LPIPS AlexNet weights (lpips.LPIPS(net='alex').state_dict() form, or BACKBONE,HEADS: "
+                    "torchvision's AlexNet and the lin layers; or 'synthetic'); without it lpips and bglpips are refused")
+    ap.add_argument("--lpips_net", default="alex", help="widths of --lpips_weights synthetic: alex, or tiny for quick CPU runs")
     return ap.parse_args(argv)
 
 
@@ -67,9 +73,12 @@ def _claim(metric_dir: Path, metrics):
     return mine
 
 
-def _compute(names, edits, sources, prompts, clip, dino=None):
+_LPIPS = ("lpips", "bglpips")
+
+
+def _compute(names, edits, sources, prompts, clip, dino=None, lpips=None, masks=None):
     """{name: tensor [B]} of one batch: the image metrics in one `image_metrics` call, the CLIP metrics in one `clip_scores` call, dinovitstruct
-    in one `dino_structure` call"""
+    in one `dino_structure` call, lpips and bglpips in one `lpips_distance` call each"""
     out = {}
     image = [n for n in names if n in IMAGE_NAMES]
     if image:
@@ -77,26 +86,31 @@ def _compute(names, edits, sources, prompts, clip, dino=None):
     if "dinovitstruct" in names:
         from metrics import dino_structure
         out["dinovitstruct"] = dino_structure(torch.cat(edits), torch.cat(sources), dino, (-1, 1))
-    other = [n for n in names if n not in IMAGE_NAMES and n != "dinovitstruct"]
+    for n in names:
+        if n in _LPIPS:
+            from metrics import lpips_distance
+            out[n] = lpips_distance(torch.cat(edits), torch.cat(sources), lpips, (-1, 1), mask=torch.stack(masks) if n == "bglpips" else None)
+    other = [n for n in names if n not in IMAGE_NAMES and n != "dinovitstruct" and n not in _LPIPS]
     if other:
         from metrics import clip_scores
         out.update(clip_scores(torch.cat(edits), torch.cat(sources), [p[0] for p in prompts], [p[1] for p in prompts], other, clip, (-1, 1)))
     return out
 
 
-def _values(names, edits, sources, prompts=None, clip=None, dino=None):
+def _values(names, edits, sources, prompts=None, clip=None, dino=None, lpips=None, masks=None):
     """{name: [float per pair]}: one call for the batch; if it raises, pair by pair and metric by metric, nan where that raises"""
     prompts = prompts or [("", "")] * len(edits)
+    masks = masks or [None] * len(edits)
     try:
-        out = _compute(names, edits, sources, prompts, clip, dino)
+        out = _compute(names, edits, sources, prompts, clip, dino, lpips, masks)
         return {n: [float(v) for v in out[n].cpu()] for n in names}
     except Exception:
         pass
     vals = {n: [] for n in names}
-    for e, s, p in zip(edits, sources, prompts):
+    for e, s, p, k in zip(edits, sources, prompts, masks):
         for n in names:
             try:
-                vals[n].append(float(_compute((n,), [e], [s], [p], clip, dino)[n][0]))
+                vals[n].append(float(_compute((n,), [e], [s], [p], clip, dino, lpips, [k])[n][0]))
             except Exception as exc:
                 print(f"{n}: nan because of {exc}")
                 vals[n].append(float("nan"))
@@ -121,8 +135,16 @@ def main(argv=None):
     if a.dino_weights is not None and "dinovitstruct" in (a.metric or []):
         from metrics import DinoModel
         dino = DinoModel(a.dino_weights, device, a.dino_model)
+    lpips = None
+    if a.lpips_weights is not None and any(m in _LPIPS for m in (a.metric or [])):
+        if "bglpips" in a.metric and a.size != 512:            # refused here, before any yaml is claimed
+            raise ValueError(f"bglpips takes the data set's 512 x 512 foreground masks: --size {a.size} is refused (the reference does not resize them either)")
+        from metrics import LpipsModel
+        paths = a.lpips_weights.split(",")
+        lpips = LpipsModel(paths[0] if len(paths) == 1 else tuple(paths), device, a.lpips_net)
     own = lambda m: ({"clip_weights": clip} if clip is not None and m.startswith("clip_") else
-                     {"dino_weights": dino, "dino_model": a.dino_model} if dino is not None and m == "dinovitstruct" else {})
+                     {"dino_weights": dino, "dino_model": a.dino_model} if dino is not None and m == "dinovitstruct" else
+                     {"lpips_weights": lpips, "lpips_net": a.lpips_net} if lpips is not None and m in _LPIPS else {})
     metrics = [EditMetric(m, input_range=(-1, 1), device=device, **own(m)) for m in (a.metric or EditMetric.get_built_metrics())]
     metric_dir = Path(a.output) / "metrics"
     metric_dir.mkdir(parents=True, exist_ok=True)
@@ -135,15 +157,15 @@ def main(argv=None):
     data = PieBenchData(a.data_path, skip_img_load=True, limit=a.limit, categories=a.categories)
     results = {n: [] for n in names}
 
-    def flush(stems, edits, sources, prompts):
+    def flush(stems, edits, sources, prompts, masks):
         if not stems:
             return
-        vals = _values(names, edits, sources, prompts, clip, dino)
+        vals = _values(names, edits, sources, prompts, clip, dino, lpips, masks)
         for (m, _), n in zip(mine, names):
             m.metric.losses.extend(vals[n])                      # what EditMetric.update records, for the whole batch
             results[n].extend({"value": v, "file": stem} for v, stem in zip(vals[n], stems))
 
-    stems, edits, sources, prompts = [], [], [], []
+    stems, edits, sources, prompts, masks = [], [], [], [], []
     for i in range(len(data)):
         s = data[i]
         edit_file = Path(a.output) / "imgs" / f"{edit_image_name(i, s['source_prompt'], s['edit']['target_prompt'])}.png"
@@ -154,8 +176,8 @@ def main(argv=None):
             e, src = preproc(edit_file), preproc(s["image_file"])
         except Exception as exc:                                 # an unreadable file: the sample's metrics "raise" (reference :97-107)
             print(f"Skipping {s['image_file']} because of {exc}")
-            flush(stems, edits, sources, prompts)                # (keeps the results in data-set order)
-            stems, edits, sources, prompts = [], [], [], []
+            flush(stems, edits, sources, prompts, masks)         # (keeps the results in data-set order)
+            stems, edits, sources, prompts, masks = [], [], [], [], []
             for (m, _), n in zip(mine, names):
                 m.metric.losses.append(float("nan"))
                 results[n].append({"value": float("nan"), "file": edit_file.stem})
@@ -164,10 +186,11 @@ def main(argv=None):
         edits.append(e)
         sources.append(src)
         prompts.append((s["source_prompt"], s["edit"]["target_prompt"]))
+        masks.append(s["mask"])
         if len(stems) == a.batch:
-            flush(stems, edits, sources, prompts)
-            stems, edits, sources, prompts = [], [], [], []
-    flush(stems, edits, sources, prompts)
+            flush(stems, edits, sources, prompts, masks)
+            stems, edits, sources, prompts, masks = [], [], [], [], []
+    flush(stems, edits, sources, prompts, masks)
     for (m, f), n in zip(mine, names):
         res = {"name": n, "mean": m.compute()[0] if results[n] else float("nan"), "results": results[n]}
         with open(f, "w") as fh:

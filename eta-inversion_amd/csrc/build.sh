@@ -3,7 +3,7 @@
 set -e
 HERE="$(cd "$(dirname "$0")" && pwd)"
 OUT="$HERE/../etainv/lib"
-OBJ="$HERE/obj"; LIBNAME=libetainv_hip.so; SRCS="step_kernels ddpm regularize proximal metrics clip dino igemm norm attention misc maps aux_nets f32path ppgemm ppconv"
+OBJ="$HERE/obj"; LIBNAME=libetainv_hip.so; SRCS="step_kernels ddpm regularize proximal metrics clip dino lpips igemm norm attention misc maps aux_nets f32path ppgemm ppconv"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result"
 mkdir -p "$OUT" "$OBJ"
 pids=()
@@ -35,8 +35,11 @@ echo "built $OUT/$LIBNAME"
 # dino.hip at 256 threads: dino_selfsim_kernel<f16 / bf16> 58 VGPRs + 32 AGPRs (the two Gram tiles' accumulators), no scratch, 36,896 B of LDS
 # (four 64 x 72 slabs: four blocks per CU); dino_selfsim_f32_kernel 86 VGPRs, no scratch, 33,824 B; dino_preprocess_kernel 19-21 VGPRs, no
 # scratch, max_rows * R * 4 B of dynamic LDS (18,816 B for 512 -> 224 at patch 8); the row-norm, GELU and finalize kernels 8-12 VGPRs, no LDS.
+# lpips.hip at 256 threads: lpips_conv2d_kernel<T, cin == 4> 44-48 VGPRs + 32 AGPRs (the 2 x 4 accumulator tiles), no scratch, 15,360 B of LDS
+# (16-bit: 192 rows of 40 elements) / 27,648 B (fp32: 192 rows of 36); maxpool3s2_kernel 38-48 VGPRs, lpips_distance_kernel 46-48 VGPRs and 32 B
+# of LDS, lpips_preprocess_kernel 29-34 VGPRs; no scratch in any of them.
 if [ "${RESOURCES:-0}" = "1" ]; then
-  for f in regularize proximal metrics dino; do
+  for f in regularize proximal metrics dino lpips; do
     hipcc $FLAGS --cuda-device-only -Rpass-analysis=kernel-resource-usage -c "$HERE/$f.hip" -o /dev/null 2>&1 | grep -E "Function Name|VGPRs|ScratchSize" || true
   done
 fi

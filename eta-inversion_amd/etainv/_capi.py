@@ -58,6 +58,11 @@ SIGNATURES = {
     "etainv_op_gelu_erf": [_p, _p, _i64, _i, _p],
     "etainv_dino_selfsim_workspace_bytes": [_i, _i],
     "etainv_dino_selfsim_mse": [_p, _i, _i, _i, _i64, _f, _p, _p, _p, _i64, _i, _p],
+    "etainv_lpips_preprocess": [_p, _p, _i, _i, _i, _i, _f, _f, _p, _i, _p],
+    "etainv_op_conv2d_relu": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "etainv_op_maxpool3s2": [_p, _p, _i, _i, _i, _i, _i, _p],
+    "etainv_lpips_distance_workspace_bytes": [_i, _i],
+    "etainv_lpips_layer_distance": [_p, _p, _i, _i, _i, _i, _p, _p, _i64, _i, _p],
     "etainv_engine_create": [C.POINTER(EngineConfig), C.POINTER(_p)],
     "etainv_engine_destroy": [_p],
     "etainv_engine_num_weights": [_p],
@@ -125,7 +130,7 @@ SIGNATURES = {
     "etainv_op_igemm_route_name": [_i],
 }
 _RESTYPES = {"etainv_last_error": C.c_char_p, "etainv_op_igemm_route_name": C.c_char_p,"etainv_engine_workspace_bytes": _i64, "etainv_image_metrics_workspace_bytes": _i64, "etainv_engine_weight_bytes": _i64,
-             "etainv_dino_selfsim_workspace_bytes": _i64}
+             "etainv_dino_selfsim_workspace_bytes": _i64, "etainv_lpips_distance_workspace_bytes": _i64}
 
 _lib = None
 

@@ -476,3 +476,67 @@ class NativeCLIP:
         ids = input_ids.to(device="cuda", dtype=torch.int64)
         hidden = self.text(ids)[0].contiguous()
         return self._head(hidden, ids.argmax(-1).to(torch.int32).contiguous(), None, self.text_projection)
+
+
+class NativeLpipsAlex:
+    """torchvision's AlexNet `features` for LPIPS, tapped after each of its five ReLUs: etainv_op_conv2d_relu (bias and ReLU in the epilogue) and
+    etainv_op_maxpool3s2 over NHWC, on the rows etainv_lpips_preprocess writes.  Weights (the names of weights.lpips_shapes) are packed once,
+    here, to [cout][kh kw][cin] by etainv_op_pack_weight mode 1 (conv1 with a zero fourth input channel); the `lin` heads stay fp32 [C].  The
+    intermediate buffers are allocated once per (n, H, W) and reused, so the taps of a call are valid until the next call with that shape."""
+
+    def __init__(self, state_dict, compute_dtype=torch.float16):
+        from .weights import LPIPS_CONVS, LPIPS_KERNELS, lpips_shapes
+        self.lib, self.cd, self.code = _capi.load(), compute_dtype, _capi.dtype_code(compute_dtype)
+        self.widths = tuple(int(state_dict[f"features.{n}.weight"].shape[0]) for n in LPIPS_CONVS)
+        for name, shape in lpips_shapes(self.widths).items():
+            if name not in state_dict or tuple(state_dict[name].shape) != tuple(shape):
+                raise ValueError(f"LPIPS state dict: {name} missing or not of shape {tuple(shape)}")
+        self.convs, self.lins, self._buffers = [], [], {}
+        for i, n in enumerate(LPIPS_CONVS):
+            w = state_dict[f"features.{n}.weight"].float()
+            if i == 0:
+                w = torch.cat([w, torch.zeros_like(w[:, :1])], 1)                 # the fourth input channel etainv_lpips_preprocess writes as 0
+            cout, cin, k, _ = w.shape
+            src, packed = _dev(w, torch.float32), torch.empty(cout, k * k, cin, dtype=compute_dtype, device="cuda")
+            _capi.check(self.lib.etainv_op_pack_weight(_capi.ptr(src), _capi.ptr(packed), cout, cin * k * k, 1, k * k, 1.0, None, self.code,
+                                                       _capi.stream_ptr()))
+            self.convs.append((packed, _dev(state_dict[f"features.{n}.bias"], torch.float32), cin, cout) + LPIPS_KERNELS[i])
+            self.lins.append(_dev(state_dict[f"lin{i}.model.1.weight"].reshape(-1), torch.float32))
+        torch.cuda.current_stream().synchronize()                                # (the fp32 sources go out of scope)
+
+    @staticmethod
+    def tap_sizes(h, w):
+        """[(H, W)] of the five taps for an h x w input"""
+        c = lambda s, k, st, p: (s + 2 * p - k) // st + 1
+        pool = lambda s: (s - 3) // 2 + 1
+        t1 = (c(h, 11, 4, 2), c(w, 11, 4, 2))
+        t2 = (pool(t1[0]), pool(t1[1]))
+        t3 = (pool(t2[0]), pool(t2[1]))
+        return [t1, t2, t3, t3, t3]
+
+    def _conv(self, x, out, n, h, w, i):
+        wt, bias, cin, cout, k, stride, pad = self.convs[i]
+        _capi.check(self.lib.etainv_op_conv2d_relu(_capi.ptr(x), _capi.ptr(wt), _capi.ptr(bias), _capi.ptr(out), n, h, w, cin, cout, k, k, stride, pad, 1,
+                                                   self.code, _capi.stream_ptr()))
+
+    def _pool(self, x, out, n, h, w, c):
+        _capi.check(self.lib.etainv_op_maxpool3s2(_capi.ptr(x), _capi.ptr(out), n, h, w, c, self.code, _capi.stream_ptr()))
+
+    def __call__(self, x_nhwc4, n):
+        """[n][H][W][4] (compute dtype, from etainv_lpips_preprocess) -> the five taps, each [n][pixels][C] in the compute dtype"""
+        assert x_nhwc4.dim() == 4 and x_nhwc4.shape[0] == n and x_nhwc4.shape[3] == 4 and x_nhwc4.dtype == self.cd, (x_nhwc4.shape, x_nhwc4.dtype)
+        h, w = int(x_nhwc4.shape[1]), int(x_nhwc4.shape[2])
+        sizes, wd = self.tap_sizes(h, w), self.widths
+        key = (n, h, w, str(x_nhwc4.device))
+        if key not in self._buffers:
+            new = lambda hw, c: torch.empty(n, hw[0] * hw[1], c, dtype=self.cd, device=x_nhwc4.device)
+            self._buffers[key] = ([new(sizes[i], wd[i]) for i in range(5)], new(sizes[1], wd[0]), new(sizes[2], wd[1]))
+        taps, p1, p2 = self._buffers[key]
+        self._conv(x_nhwc4, taps[0], n, h, w, 0)
+        self._pool(taps[0], p1, n, *sizes[0], wd[0])
+        self._conv(p1, taps[1], n, *sizes[1], 1)
+        self._pool(taps[1], p2, n, *sizes[1], wd[1])
+        self._conv(p2, taps[2], n, *sizes[2], 2)
+        self._conv(taps[2], taps[3], n, *sizes[2], 3)
+        self._conv(taps[3], taps[4], n, *sizes[2], 4)
+        return taps

@@ -227,3 +227,79 @@ def load_dino_state_dict(path) -> dict:
     if missing:
         raise ValueError(f"not a DINO ViT state dict: {', '.join(missing)} missing")
     return out
+
+
+# ---- LPIPS (the lpips / bglpips metrics' model): torchvision's AlexNet `features` and the five 1x1 `lin` heads of lpips.LPIPS(net='alex')
+LPIPS_CONVS = (0, 3, 6, 8, 10)                                      # positions of the five convolutions in torchvision's `features`
+LPIPS_KERNELS = ((11, 4, 2), (5, 1, 2), (3, 1, 1), (3, 1, 1), (3, 1, 1))   # (kernel, stride, pad) per convolution
+LPIPS_WIDTHS = {"alex": (64, 192, 384, 256, 256), "tiny": (16, 32, 48, 32, 32)}   # "tiny": synthetic weights only, quick CPU runs
+LPIPS_SHIFT, LPIPS_SCALE = (-.030, -.088, -.188), (.458, .448, .450)
+
+
+def lpips_shapes(widths) -> dict:
+    """name -> shape of every tensor the LPIPS tower reads, under the loader's own names: features.N.{weight, bias}, lin{i}.model.1.weight"""
+    shapes, cin = {}, 3
+    for i, (n, c) in enumerate(zip(LPIPS_CONVS, widths)):
+        k = LPIPS_KERNELS[i][0]
+        shapes[f"features.{n}.weight"], shapes[f"features.{n}.bias"], shapes[f"lin{i}.model.1.weight"] = (c, cin, k, k), (c,), (1, c, 1, 1)
+        cin = c
+    return shapes
+
+
+def synthetic_lpips_state_dict(seed=0, net="alex") -> dict:
+    """every parameter the LPIPS tower reads, synthetic: He-scaled convolutions N(0, 2 / fan_in) so that activations stay O(1) through the
+    five ReLUs, biases 0.05 N(0, 1) (both signs), `lin` weights U(0, 4 / C) (non-negative, of order 1 / C, as the trained heads are)"""
+    if net not in LPIPS_WIDTHS:
+        raise ValueError(f"lpips net must be one of {', '.join(LPIPS_WIDTHS)}, got {net}")
+    out = {}
+    for name, shape in lpips_shapes(LPIPS_WIDTHS[net]).items():
+        g = torch.Generator().manual_seed((zlib.crc32(("lpips." + net + "." + name).encode()) + 1000003 * seed) & 0x7FFFFFFF)
+        if name.startswith("lin"):
+            out[name] = torch.rand(shape, generator=g) * (4.0 / shape[1])
+        elif name.endswith(".bias"):
+            out[name] = 0.05 * torch.randn(shape, generator=g)
+        else:
+            out[name] = torch.randn(shape, generator=g) * math.sqrt(2.0 / (shape[1] * shape[2] * shape[3]))
+    return out
+
+
+def load_lpips_state_dict(weights) -> dict:
+    """The LPIPS (v0.1, AlexNet) parameters at `weights`, fp32, under the names of `lpips_shapes`.  Accepted: a path or a dict in the form of
+    lpips.LPIPS(net='alex').state_dict() (`net.slice{1..5}.{0,3,6,8,10}.{weight,bias}`, and `lin{i}.model.1.weight` or
+    `lins.{i}.model.1.weight`); torchvision's AlexNet names (`features.{0,3,6,8,10}.*`) together with the `lin{i}` keys; or a pair
+    (backbone, linear heads) of paths or dicts, merged.  Keys are matched by their suffix, so any prefix (`module.`, `net.`) is taken.  A
+    `scaling_layer.shift` / `.scale` in the file must equal LPIPS's constants: the kernels hold them.  Shapes are checked, and a refusal
+    names the missing key.  NOT VERIFIED against a trained file: neither the lpips package nor torchvision's checkpoint was at hand when this
+    was written, and the key names above are restated from memory."""
+    import re
+    parts = weights if isinstance(weights, (tuple, list)) else [weights]
+    merged = {}
+    for part in parts:
+        sd = part if isinstance(part, dict) else torch.load(str(part), map_location="cpu", weights_only=True)
+        if "state_dict" in sd and isinstance(sd["state_dict"], dict):
+            sd = sd["state_dict"]
+        merged.update({k: v for k, v in sd.items() if torch.is_tensor(v)})
+    out = {}
+    conv = re.compile(r"(^|\.)(features|slice[1-5])\.(0|3|6|8|10)\.(weight|bias)$")
+    lin = re.compile(r"(^|\.)lins?\.?([0-4])\.model\.1\.weight$")
+    for k, v in merged.items():
+        m = conv.search(k)
+        if m:
+            out[f"features.{m.group(3)}.{m.group(4)}"] = v.detach().float()
+            continue
+        m = lin.search(k)
+        if m:
+            out[f"lin{m.group(2)}.model.1.weight"] = v.detach().float().reshape(1, -1, 1, 1)
+            continue
+        for name, want in (("shift", LPIPS_SHIFT), ("scale", LPIPS_SCALE)):
+            if k.endswith("scaling_layer." + name) and not torch.allclose(v.detach().float().flatten(), torch.tensor(want), rtol=0, atol=1e-6):
+                raise ValueError(f"LPIPS state dict: {k} is {v.flatten().tolist()}, but the kernels hold {want}")
+    if "features.0.weight" not in out and "lin0.model.1.weight" not in out:
+        raise ValueError("not an LPIPS state dict: neither features.0.weight (net.slice1.0.weight) nor lin0.model.1.weight found")
+    widths = [out[f"features.{n}.weight"].shape[0] if f"features.{n}.weight" in out else 0 for n in LPIPS_CONVS]
+    for name, shape in lpips_shapes(widths).items():
+        if name not in out:
+            raise ValueError(f"LPIPS state dict: {name} missing")
+        if tuple(out[name].shape) != tuple(shape):
+            raise ValueError(f"LPIPS state dict: {name} has shape {tuple(out[name].shape)}, expected {tuple(shape)}")
+    return out

@@ -268,6 +268,38 @@ int64_t etainv_dino_selfsim_workspace_bytes(int b, int n);
 int etainv_dino_selfsim_mse(const void* keys, int b, int n, int d, int64_t ld, float eps, double* scores_out, float* norms_out, void* workspace,
                             int64_t workspace_bytes, int dtype, void* stream);
 
+/* ---- lpips, bglpips (reference metrics/metrics.py:40-61, metrics/bglpips.py:27-52 and :141-148; LPIPS v0.1, net='alex', lpips=True,
+ * spatial=False, eval mode): image preprocessing, the AlexNet tower's convolution and pooling, and the per-tap distance.
+ *
+ * etainv_lpips_preprocess: `_normalize`, `* 2 - 1` (metrics.py:51-60, bglpips.py:142-146), the background mask (bglpips.py:49-51, :91) and
+ *   LPIPS's scaling layer for n images in one launch.  x [n][3][h][w] fp32 in (lo, hi) -> v = 2 (x - lo) / (hi - lo) - 1 -> (mask given)
+ *   v (1 - mask[i % n_mask]), mask [n_mask][h][w] fp32 with foreground = 1: applied after the map to [-1, 1], so the foreground becomes 0 ->
+ *   (v - shift) / scale with shift (-.030, -.088, -.188), scale (.458, .448, .450) -> out [n][h][w][4] NHWC in `dtype`, the fourth channel 0.
+ *   The arithmetic is float64, rounded once.  n_mask is read only when mask is given.  h != w is allowed.
+ * etainv_op_conv2d_relu: torchvision AlexNet `features` convolutions (conv 11x11 stride 4 pad 2, 5x5 pad 2, 3x3 pad 1) with their ReLU, as one
+ *   implicit GEMM over NHWC: x [n][h][w][cin], w [cout][kh kw][cin] (etainv_op_pack_weight mode 1 of the OIHW tensor; conv1: a zero fourth
+ *   input channel), bias [cout] fp32 or null, out [n][ho][wo][cout] with ho = (h + 2 pad - kh) / stride + 1 (floor), relu != 0: max(., 0).
+ *   kh, kw <= 11, stride 1 or 4, pad <= 2; fp32 accumulation on MFMA (fp32 operands: the f32-input matrix instruction, the parity mode).  The
+ *   kernel gathers its own activation tile; nothing is im2col'ed to memory.  Refused before any launch: a null or misaligned pointer (x, w, out
+ *   16 bytes), an output smaller than 1 x 1, cin other than 4 or a multiple of 32, cout not a multiple of 4, a stride, pad or kernel size outside
+ *   the above.
+ * etainv_op_maxpool3s2: MaxPool2d(3, 2) of `features` (floor mode, no pad) over NHWC [n][h][w][c] -> [n][(h - 3) / 2 + 1][(w - 3) / 2 + 1][c];
+ *   any sign of input; c a whole number of 16-byte vectors.
+ * etainv_lpips_layer_distance: LPIPS's normalize_tensor, `lin` layer and spatial_average for one tap of b pairs.  feats [2 b][pixels][c] in
+ *   `dtype`: rows 0 .. b-1 the sources' features, b .. 2 b-1 the edits'; lin_w [c] fp32 (no bias).  Per pixel alpha = sqrt(sum_c a_c^2) + 1e-10
+ *   (the epsilon is added to the norm), beta likewise; out[pair] (+)= mean over the pixels of sum_c lin_w[c] (a_c / alpha - b_c / beta)^2,
+ *   float64 from the loaded features on, every sum in a fixed order without atomics.  accumulate = 1 adds to out[pair] (the five taps, in the
+ *   caller's order), 0 overwrites.  Bit-identical from run to run and for any b; exactly 0.0 for identical features; unchanged when the sides
+ *   are swapped.  workspace: at least etainv_lpips_distance_workspace_bytes(b, pixels) bytes (-1: refused), 8-byte aligned. */
+int etainv_lpips_preprocess(const float* x, const float* mask, int n, int n_mask, int h, int w, float lo, float hi, void* out, int dtype,
+                            void* stream);
+int etainv_op_conv2d_relu(const void* x, const void* w, const float* bias, void* out, int n, int h, int wd, int cin, int cout, int kh, int kw,
+                          int stride, int pad, int relu, int dtype, void* stream);
+int etainv_op_maxpool3s2(const void* x, void* out, int n, int h, int w, int c, int dtype, void* stream);
+int64_t etainv_lpips_distance_workspace_bytes(int b, int pixels);
+int etainv_lpips_layer_distance(const void* feats, const float* lin_w, int b, int pixels, int c, int accumulate, double* out, void* workspace,
+                                int64_t workspace_bytes, int dtype, void* stream);
+
 /* ---------------------------------------------------------------- engine */
 typedef struct etainv_engine etainv_engine_t;
 
