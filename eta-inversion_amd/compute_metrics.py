@@ -5,6 +5,7 @@
                               [--batch 32] [--device cuda|cpu] [--size 512] [--limit N] [--categories 1_change_object ...]
                               [--clip_weights PATH|synthetic] [--clip_tokenizer DIR] [--clip_templates FILE] [--clip_model ViT-B/16]
                               [--dino_weights PATH|synthetic] [--dino_model dino_vitb8]
+                              [--dinov2_weights PATH|synthetic] [--dinov2_model dinov2_vitb14]
                               [--lpips_weights PATH[,PATH]|synthetic] [--lpips_net alex]
 
 Reads the layout eval.py writes, `<output>/imgs/{i:04d}_{source}_{target}.png`, next to the data set's source images.  Kept from the reference:
@@ -16,7 +17,8 @@ that are built (EditMetric refuses the others by name).  The CLIP metrics (clip_
 computed only when --clip_weights hands their weights over (a transformers CLIPModel state dict or an OpenAI clip checkpoint; "synthetic" with
 --clip_model for dry runs): the data set's prompts go with every pair into one `clip_scores` call per batch.  --clip_templates FILE: one caption
 template per line, each with a {} for the prompt.  dinovitstruct is computed only when --dino_weights hands DINO's checkpoint over ("synthetic" with
---dino_model for dry runs): one `dino_structure` call per batch.  lpips and bglpips are computed only when --lpips_weights hands the LPIPS AlexNet
+--dino_model for dry runs): one `dino_structure` call per batch; dinovitstruct_v2 likewise with --dinov2_weights (a published dinov2_vit{s,b,l}14
+backbone checkpoint; "synthetic" with --dinov2_model).  lpips and bglpips are computed only when --lpips_weights hands the LPIPS AlexNet
 over (one file in lpips.LPIPS's state-dict form, or backbone,heads; "synthetic" for dry runs): one `lpips_distance` call per batch and per name,
 bglpips with the data set's foreground masks, which are 512 x 512: any other --size is refused for it."""
 import argparse
@@ -53,6 +55,9 @@ def parse_args(argv=None):
     ap.add_argument("--dino_weights", default=None, help="DINO ViT weights (the published checkpoint, a state dict file, or 'synthetic'); without it "
                     "dinovitstruct is refused")
     ap.add_argument("--dino_model", default="dino_vitb8", help="the metric's model name; geometry of --dino_weights synthetic")
+    ap.add_argument("--dinov2_weights", default=None, help="DINOv2 ViT weights (a published dinov2_vit{s,b,l}14 backbone checkpoint, a state dict file, "
+                    "or 'synthetic'); without it dinovitstruct_v2 is refused")
+    ap.add_argument("--dinov2_model", default="dinov2_vitb14", help="the metric's model name; geometry of --dinov2_weights synthetic")
     ap.add_argument("--lpips_weights", default=None, help="LPIPS AlexNet weights (lpips.LPIPS(net='alex').state_dict() form, or BACKBONE,HEADS: "
                     "torchvision's AlexNet and the lin layers; or 'synthetic'); without it lpips and bglpips are refused")
     ap.add_argument("--lpips_net", default="alex", help="widths of --lpips_weights synthetic: alex, or tiny for quick CPU runs")
@@ -76,9 +81,9 @@ def _claim(metric_dir: Path, metrics):
 _LPIPS = ("lpips", "bglpips")
 
 
-def _compute(names, edits, sources, prompts, clip, dino=None, lpips=None, masks=None):
+def _compute(names, edits, sources, prompts, clip, dino=None, lpips=None, masks=None, dinov2=None):
     """{name: tensor [B]} of one batch: the image metrics in one `image_metrics` call, the CLIP metrics in one `clip_scores` call, dinovitstruct
-    in one `dino_structure` call, lpips and bglpips in one `lpips_distance` call each"""
+    (and dinovitstruct_v2) in one `dino_structure` call, lpips and bglpips in one `lpips_distance` call each"""
     out = {}
     image = [n for n in names if n in IMAGE_NAMES]
     if image:
@@ -86,23 +91,26 @@ def _compute(names, edits, sources, prompts, clip, dino=None, lpips=None, masks=
     if "dinovitstruct" in names:
         from metrics import dino_structure
         out["dinovitstruct"] = dino_structure(torch.cat(edits), torch.cat(sources), dino, (-1, 1))
+    if "dinovitstruct_v2" in names:
+        from metrics import dino_structure
+        out["dinovitstruct_v2"] = dino_structure(torch.cat(edits), torch.cat(sources), dinov2, (-1, 1))
     for n in names:
         if n in _LPIPS:
             from metrics import lpips_distance
             out[n] = lpips_distance(torch.cat(edits), torch.cat(sources), lpips, (-1, 1), mask=torch.stack(masks) if n == "bglpips" else None)
-    other = [n for n in names if n not in IMAGE_NAMES and n != "dinovitstruct" and n not in _LPIPS]
+    other = [n for n in names if n not in IMAGE_NAMES and n not in ("dinovitstruct", "dinovitstruct_v2") and n not in _LPIPS]
     if other:
         from metrics import clip_scores
         out.update(clip_scores(torch.cat(edits), torch.cat(sources), [p[0] for p in prompts], [p[1] for p in prompts], other, clip, (-1, 1)))
     return out
 
 
-def _values(names, edits, sources, prompts=None, clip=None, dino=None, lpips=None, masks=None):
+def _values(names, edits, sources, prompts=None, clip=None, dino=None, lpips=None, masks=None, dinov2=None):
     """{name: [float per pair]}: one call for the batch; if it raises, pair by pair and metric by metric, nan where that raises"""
     prompts = prompts or [("", "")] * len(edits)
     masks = masks or [None] * len(edits)
     try:
-        out = _compute(names, edits, sources, prompts, clip, dino, lpips, masks)
+        out = _compute(names, edits, sources, prompts, clip, dino, lpips, masks, dinov2)
         return {n: [float(v) for v in out[n].cpu()] for n in names}
     except Exception:
         pass
@@ -110,7 +118,7 @@ def _values(names, edits, sources, prompts=None, clip=None, dino=None, lpips=Non
     for e, s, p, k in zip(edits, sources, prompts, masks):
         for n in names:
             try:
-                vals[n].append(float(_compute((n,), [e], [s], [p], clip, dino, lpips, [k])[n][0]))
+                vals[n].append(float(_compute((n,), [e], [s], [p], clip, dino, lpips, [k], dinov2)[n][0]))
             except Exception as exc:
                 print(f"{n}: nan because of {exc}")
                 vals[n].append(float("nan"))
@@ -135,6 +143,10 @@ def main(argv=None):
     if a.dino_weights is not None and "dinovitstruct" in (a.metric or []):
         from metrics import DinoModel
         dino = DinoModel(a.dino_weights, device, a.dino_model)
+    dinov2 = None
+    if a.dinov2_weights is not None and "dinovitstruct_v2" in (a.metric or []):
+        from metrics import Dinov2Model
+        dinov2 = Dinov2Model(a.dinov2_weights, device, a.dinov2_model)
     lpips = None
     if a.lpips_weights is not None and any(m in _LPIPS for m in (a.metric or [])):
         if "bglpips" in a.metric and a.size != 512:            # refused here, before any yaml is claimed
@@ -144,6 +156,7 @@ def main(argv=None):
         lpips = LpipsModel(paths[0] if len(paths) == 1 else tuple(paths), device, a.lpips_net)
     own = lambda m: ({"clip_weights": clip} if clip is not None and m.startswith("clip_") else
                      {"dino_weights": dino, "dino_model": a.dino_model} if dino is not None and m == "dinovitstruct" else
+                     {"dinov2_weights": dinov2, "dinov2_model": a.dinov2_model} if dinov2 is not None and m == "dinovitstruct_v2" else
                      {"lpips_weights": lpips, "lpips_net": a.lpips_net} if lpips is not None and m in _LPIPS else {})
     metrics = [EditMetric(m, input_range=(-1, 1), device=device, **own(m)) for m in (a.metric or EditMetric.get_built_metrics())]
     metric_dir = Path(a.output) / "metrics"
@@ -160,7 +173,7 @@ def main(argv=None):
     def flush(stems, edits, sources, prompts, masks):
         if not stems:
             return
-        vals = _values(names, edits, sources, prompts, clip, dino, lpips, masks)
+        vals = _values(names, edits, sources, prompts, clip, dino, lpips, masks, dinov2)
         for (m, _), n in zip(mine, names):
             m.metric.losses.extend(vals[n])                      # what EditMetric.update records, for the whole batch
             results[n].extend({"value": v, "file": stem} for v, stem in zip(vals[n], stems))

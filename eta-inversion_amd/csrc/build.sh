@@ -35,11 +35,12 @@ echo "built $OUT/$LIBNAME"
 # dino.hip at 256 threads: dino_selfsim_kernel<f16 / bf16> 58 VGPRs + 32 AGPRs (the two Gram tiles' accumulators), no scratch, 36,896 B of LDS
 # (four 64 x 72 slabs: four blocks per CU); dino_selfsim_f32_kernel 86 VGPRs, no scratch, 33,824 B; dino_preprocess_kernel 19-21 VGPRs, no
 # scratch, max_rows * R * 4 B of dynamic LDS (18,816 B for 512 -> 224 at patch 8); the row-norm, GELU and finalize kernels 8-12 VGPRs, no LDS.
+# norm.hip at 256 threads: layerscale_add_layernorm_kernel<f16 / bf16> 60 VGPRs, <float> 59, layernorm_kernel 56; no scratch, no LDS, 8 waves per SIMD.
 # lpips.hip at 256 threads: lpips_conv2d_kernel<T, cin == 4> 44-48 VGPRs + 32 AGPRs (the 2 x 4 accumulator tiles), no scratch, 15,360 B of LDS
 # (16-bit: 192 rows of 40 elements) / 27,648 B (fp32: 192 rows of 36); maxpool3s2_kernel 38-48 VGPRs, lpips_distance_kernel 46-48 VGPRs and 32 B
 # of LDS, lpips_preprocess_kernel 29-34 VGPRs; no scratch in any of them.
 if [ "${RESOURCES:-0}" = "1" ]; then
-  for f in regularize proximal metrics dino lpips; do
+  for f in regularize proximal metrics dino lpips norm; do
     hipcc $FLAGS --cuda-device-only -Rpass-analysis=kernel-resource-usage -c "$HERE/$f.hip" -o /dev/null 2>&1 | grep -E "Function Name|VGPRs|ScratchSize" || true
   done
 fi

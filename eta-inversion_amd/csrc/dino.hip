@@ -1,5 +1,7 @@
 // The dinovitstruct metric's own kernels (reference metrics/dino_vit_structure.py): from B image pairs to B structure distances.  The DINO ViT
 // tower between them runs on the GEMM / LayerNorm kernels, etainv_clip_assemble_tokens and etainv_op_vit_attention (etainv/nets.py).
+// dinovitstruct_v2 (DINOv2, patch 14) takes the same preprocess kernel with a padded row stride (etainv_dinov2_preprocess: rows of 640 for
+// 3 * 14^2 = 588 values, the tail written as zero) and adds etainv_op_layerscale_add_layernorm, whose kernel sits beside LayerNorm in norm.hip.
 //   preprocess  grid (R / p, B): SimpleMetric._normalize, Resize(224) on a float tensor and the ImageNet normalisation (:236-241, :258-259) for
 //               one band of p output rows of one image.  Per channel: the horizontal pass reads the band's input rows from global memory,
 //               (x - lo) / (hi - lo) per tap, into LDS [rows][R] fp32 (never the raw rows at full width: 512 -> 224 at p = 8 spans 21 input rows);
@@ -32,15 +34,15 @@ struct DinoPreParams {
   const float* wh;            //             weights [R][ks_h]
   const int32_t* bv;          // vertical
   const float* wv;
-  void* rows;                 // [B g g][3 p^2]
-  int S, R, P, ks_h, ks_v, max_rows;
+  void* rows;                 // [B g g][ld], ld >= 3 p^2: columns 3 p^2 .. ld-1 are written as zero
+  int S, R, P, ld, ks_h, ks_v, max_rows;
   float lo, span;
 };
 
 template <typename T>
 __global__ void __launch_bounds__(DINO_THREADS) dino_preprocess_kernel(DinoPreParams p) {
   extern __shared__ float dino_smem[];                     // [max_rows][R]: the band's input rows of one channel after the horizontal pass
-  const int S = p.S, R = p.R, P = p.P, g = R / P, Kp = 3 * P * P;
+  const int S = p.S, R = p.R, P = p.P, g = R / P, K = 3 * P * P, ld = p.ld;
   const int tid = threadIdx.x, band = blockIdx.x;
   const int64_t b = blockIdx.y;
   const int y0 = band * P, y1 = y0 + P - 1;
@@ -49,7 +51,11 @@ __global__ void __launch_bounds__(DINO_THREADS) dino_preprocess_kernel(DinoPrePa
   const int nrows = min(min(max(p.bv[2 * y1] + p.bv[2 * y1 + 1], row0 + 1), S) - row0, p.max_rows);
   // normalised in float64 and rounded once: (v - mean) cancels near the mean
   const double mean[3] = {0.485, 0.456, 0.406}, stdv[3] = {0.229, 0.224, 0.225};
-  T* rows = (T*)p.rows + ((b * g + band) * g) * (int64_t)Kp;
+  T* rows = (T*)p.rows + ((b * g + band) * g) * (int64_t)ld;
+  for (int i = tid; i < g * (ld - K); i += DINO_THREADS) {            // the padding of the band's g rows
+    const int patch = i / (ld - K);
+    rows[(int64_t)patch * ld + K + (i - patch * (ld - K))] = from_f32<T>(0.f);
+  }
 
   for (int c = 0; c < 3; ++c) {
     const float* src = p.x + ((b * 3 + c) * S + row0) * (int64_t)S;
@@ -70,18 +76,20 @@ __global__ void __launch_bounds__(DINO_THREADS) dino_preprocess_kernel(DinoPrePa
       float acc = 0.f;
       for (int j = 0; j < cnt; ++j) acc = fmaf(w[j], dino_smem[min(max(r0 + j, 0), nrows - 1) * R + xo], acc);
       const int patch = xo / P, pxx = xo - patch * P;
-      rows[(int64_t)patch * Kp + (c * P + py) * P + pxx] = from_f32<T>((float)(((double)acc - mean[c]) / stdv[c]));
+      rows[(int64_t)patch * ld + (c * P + py) * P + pxx] = from_f32<T>((float)(((double)acc - mean[c]) / stdv[c]));
     }
     __syncthreads();                    // (the next channel's horizontal pass overwrites what the vertical pass reads)
   }
 }
 
-static int launch_dino_preprocess(const float* x, int b, int s, int r, int p, float lo, float hi, const int32_t* bh, const float* wh, int ks_h,
+// ld: the row stride of rows_out in elements (3 p^2 for DINO; 640 for DINOv2's patch 14).  The entry points check p; everything else is checked here.
+static int launch_dino_preprocess(const float* x, int b, int s, int r, int p, int ld, float lo, float hi, const int32_t* bh, const float* wh, int ks_h,
                                   const int32_t* bv, const float* wv, int ks_v, int max_rows, void* rows, int dtype, hipStream_t st) {
   ETAINV_CHECK(x && bh && wh && bv && wv && rows, "null pointer: x, the four tables and rows_out are required");
   ETAINV_CHECK((((uintptr_t)x | (uintptr_t)bh | (uintptr_t)wh | (uintptr_t)bv | (uintptr_t)wv) & 3) == 0 && ((uintptr_t)rows & 15) == 0,
                "x and the tables must be 4-byte aligned, rows_out 16-byte aligned");
-  ETAINV_CHECK(p == 8 || p == 16, "patch size must be 8 or 16");
+  ETAINV_CHECK(dtype == ETAINV_F32 || dtype == ETAINV_F16 || dtype == ETAINV_BF16, "bad dtype");
+  ETAINV_CHECK(p >= 1 && ld >= 3 * p * p && (ld * (dtype == ETAINV_F32 ? 4 : 2)) % 16 == 0, "the row stride must hold 3 p^2 values and be whole 16-byte vectors");
   ETAINV_CHECK(r >= p && r % p == 0 && r <= 4096, "the resized side R must be a multiple of the patch size (at most 4096)");
   ETAINV_CHECK(b >= 0 && b <= 65535 && s >= 1 && s <= 16384, "b must be in [0, 65535] and s in [1, 16384]");
   ETAINV_CHECK(ks_h >= 1 && ks_v >= 1 && max_rows >= 1 && max_rows <= s, "tap counts and max_rows must be positive, max_rows at most s");
@@ -89,7 +97,7 @@ static int launch_dino_preprocess(const float* x, int b, int s, int r, int p, fl
   const size_t lds = (size_t)max_rows * (size_t)r * sizeof(float);
   ETAINV_CHECK(lds <= 65536, "a band of p output rows needs max_rows * r * 4 bytes of LDS, at most 65536: the image is too large for this resize");
   if (b == 0) return 0;
-  DinoPreParams q = {x, bh, wh, bv, wv, rows, s, r, p, ks_h, ks_v, max_rows, lo, hi - lo};
+  DinoPreParams q = {x, bh, wh, bv, wv, rows, s, r, p, ld, ks_h, ks_v, max_rows, lo, hi - lo};
   ETAINV_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(dino_preprocess_kernel<T>, dim3(r / p, b), dim3(DINO_THREADS), lds, st, q));
   ETAINV_LAUNCH_CHECK();
   return 0;
@@ -374,8 +382,25 @@ using namespace etainv;
 extern "C" int etainv_dino_preprocess(const float* x, int b, int s, int r, int p, float lo, float hi, const int32_t* bounds_h, const float* coef_h,
                                       int ksize_h, const int32_t* bounds_v, const float* coef_v, int ksize_v, int max_rows, void* rows_out, int dtype,
                                       void* stream) {
-  DINO_ENTRY("etainv_dino_preprocess", launch_dino_preprocess(x, b, s, r, p, lo, hi, bounds_h, coef_h, ksize_h, bounds_v, coef_v, ksize_v, max_rows,
-                                                              rows_out, dtype, (hipStream_t)stream));
+  if (p != 8 && p != 16) {
+    set_error("etainv_dino_preprocess: patch size must be 8 or 16");
+    return 1;
+  }
+  DINO_ENTRY("etainv_dino_preprocess", launch_dino_preprocess(x, b, s, r, p, 3 * p * p, lo, hi, bounds_h, coef_h, ksize_h, bounds_v, coef_v, ksize_v,
+                                                              max_rows, rows_out, dtype, (hipStream_t)stream));
+}
+
+extern "C" int etainv_dinov2_preprocess(const float* x, int b, int s, int r, float lo, float hi, const int32_t* bounds_h, const float* coef_h, int ksize_h,
+                                        const int32_t* bounds_v, const float* coef_v, int ksize_v, int max_rows, void* rows_out, int dtype,
+                                        void* stream) {
+  DINO_ENTRY("etainv_dinov2_preprocess", launch_dino_preprocess(x, b, s, r, 14, ETAINV_DINOV2_KP, lo, hi, bounds_h, coef_h, ksize_h, bounds_v, coef_v,
+                                                                ksize_v, max_rows, rows_out, dtype, (hipStream_t)stream));
+}
+
+extern "C" int etainv_op_layerscale_add_layernorm(const void* y, const float* ls_gamma, const void* x, const float* ln_gamma, const float* ln_beta,
+                                                  float eps, void* x_out, void* h_out, int rows, int c, int dtype, void* stream) {
+  DINO_ENTRY("etainv_op_layerscale_add_layernorm", launch_layerscale_add_layernorm(y, ls_gamma, x, ln_gamma, ln_beta, eps, x_out, h_out, rows, c, dtype,
+                                                                                   (hipStream_t)stream));
 }
 
 extern "C" int etainv_op_gelu_erf(const void* x, void* out, int64_t n, int dtype, void* stream) {

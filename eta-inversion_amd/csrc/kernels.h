@@ -151,6 +151,9 @@ int launch_gn_fold(const float* w, const float* gamma, const float* beta, const 
                    void* wb_out, float* cb_out, int dtype, hipStream_t s);
 int launch_layernorm(const void* x, const float* gamma, const float* beta, void* out, int rows, int c, float eps, int dtype,
                      hipStream_t s);
+// x_out = round(x + ls_gamma * y) (optional store) and h_out = LayerNorm(x_out as stored), one wave per row; fp16, bf16 and fp32
+int launch_layerscale_add_layernorm(const void* y, const float* ls_gamma, const void* x, const float* ln_gamma, const float* ln_beta, float eps, void* x_out,
+                                    void* h_out, int rows, int c, int dtype, hipStream_t s);
 // stat[row] = (mean, rstd) of x[row][0..c): IGemmParams::ln_stat computed by a pass over x (when the producing GEMM could not emit partials)
 int launch_row_stats(const void* x, float* stat, int rows, int c, float eps, int dtype, hipStream_t s);
 // partials[row][P] (mean, M2) pairs over cw columns each (IGemmParams::stat_out) -> stat[row] = (mean, rstd); Chan's update in index order

@@ -5,6 +5,8 @@
 // GroupNorm runs as stats -> apply (the apply blocks reduce the per-chunk partial sums themselves).  The stats/apply kernels read up to two source tensors so
 // the decoder's torch.cat([x, skip], dim=1) is consumed in place; `apply` writes the concatenated,
 // normalised (and SiLU'd) tensor that feeds the following 3x3 convolution.
+#include <cmath>
+
 #include "common.h"
 #include "kernels.h"
 
@@ -284,14 +286,23 @@ __global__ void __launch_bounds__(256) gn_apply_kernel(const T* __restrict__ x1,
   }
 }
 
-// one wave per row, row kept in registers (C <= 1536), exact two-pass mean/variance
-template <typename T>
-__global__ void __launch_bounds__(256) layernorm_kernel(const T* __restrict__ x, const float* __restrict__ gamma,
-                                                        const float* __restrict__ beta, T* __restrict__ out, int rows, int C,
-                                                        float eps) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
+// fp32 rows take the same lanes: a vector of 8 is two 16-byte pieces (the fused LayerScale kernel below; plain fp32 LayerNorm is f32path.hip's)
+__device__ __forceinline__ void load8(const float* p, float (&v)[8]) {
+  const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { v[j] = a[j]; v[4 + j] = b[j]; }
+}
+__device__ __forceinline__ void store8(float* p, const float (&v)[8]) {
+  *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
+  *reinterpret_cast<f32x4*>(p + 4) = f32x4{v[4], v[5], v[6], v[7]};
+}
+
+// LayerNorm of one row held by one wave: lane l owns the vectors of 8 l, l + 64, l + 128 (those below C / 8), fetched by load(v, t) into registers;
+// exact two-pass mean and variance, a lane's terms in index order, then the xor butterfly; before(v, t) runs in front of each output store.  The
+// body of layernorm_kernel and of layerscale_add_layernorm_kernel, so that the two give the same bits on the same row.
+template <typename T, typename Load, typename Before>
+__device__ __forceinline__ void ln_row(int lane, int C, const float* __restrict__ gamma, const float* __restrict__ beta, float eps, T* out, Load load,
+                                       Before before) {
   const int nvec = C >> 3;
   float t[3][8];
   float sum = 0.f;
@@ -299,7 +310,7 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const T* __restrict__ x,
   for (int i = 0; i < 3; ++i) {
     const int v = lane + 64 * i;
     if (v < nvec) {
-      load8(x + (int64_t)row * C + v * 8, t[i]);
+      load(v, t[i]);
 #pragma unroll
       for (int j = 0; j < 8; ++j) sum += t[i][j];
     }
@@ -319,12 +330,51 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const T* __restrict__ x,
   for (int i = 0; i < 3; ++i) {
     const int v = lane + 64 * i;
     if (v < nvec) {
+      before(v, t[i]);
       float o[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) o[j] = (t[i][j] - mean) * rstd * gamma[v * 8 + j] + beta[v * 8 + j];
-      store8(out + (int64_t)row * C + v * 8, o);
+      store8(out + v * 8, o);
     }
   }
+}
+
+// one wave per row, row kept in registers (C <= 1536), exact two-pass mean/variance
+template <typename T>
+__global__ void __launch_bounds__(256) layernorm_kernel(const T* __restrict__ x, const float* __restrict__ gamma,
+                                                        const float* __restrict__ beta, T* __restrict__ out, int rows, int C,
+                                                        float eps) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const T* xr = x + (int64_t)row * C;
+  ln_row(lane, C, gamma, beta, eps, out + (int64_t)row * C, [&](int v, float (&t)[8]) { load8(xr + v * 8, t); }, [](int, const float (&)[8]) {});
+}
+
+// DINOv2's residual step and the LayerNorm behind it in one pass (etainv_op_layerscale_add_layernorm): per row, x_out = round_T(x + ls y) with
+// one fp32 FMA per element, h_out = LayerNorm(x_out as stored).  One wave per row as above; the wave reads its whole row of y and x before it
+// writes anything (both outputs are stored in the last loop), so x_out may be x; neither is __restrict__.  x_out may be null (the tower's last
+// step needs h_out alone).
+template <typename T>
+__global__ void __launch_bounds__(256) layerscale_add_layernorm_kernel(const T* __restrict__ y, const float* __restrict__ ls, const T* x,
+                                                                       const float* __restrict__ gamma, const float* __restrict__ beta, T* x_out,
+                                                                       T* __restrict__ h_out, int rows, int C, float eps) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int64_t base = (int64_t)row * C;
+  ln_row(lane, C, gamma, beta, eps, h_out + base,
+         [&](int v, float (&t)[8]) {
+           float a[8], g[8];
+           load8(y + base + v * 8, a);
+           load8(x + base + v * 8, t);
+           load8(ls + v * 8, g);
+#pragma unroll
+           for (int j = 0; j < 8; ++j) t[j] = to_f32(from_f32<T>(fmaf(g[j], a[j], t[j])));
+         },
+         [&](int v, const float (&t)[8]) {
+           if (x_out) store8(x_out + base + v * 8, t);
+         });
 }
 
 // Row statistics alone, (mean, rstd) as the LayerNorm-folded GEMMs read them (igemm.hip, IGemmParams::ln_stat): the fallback when the GEMM that
@@ -542,6 +592,25 @@ int launch_layernorm(const void* x, const float* gamma, const float* beta, void*
   ETAINV_DISPATCH_HALF(dtype, T,
                        hipLaunchKernelGGL(layernorm_kernel<T>, dim3(cdiv(rows, 4)), dim3(256), 0, s, (const T*)x, gamma, beta,
                                           (T*)out, rows, c, eps));
+  ETAINV_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_layerscale_add_layernorm(const void* y, const float* ls_gamma, const void* x, const float* ln_gamma, const float* ln_beta, float eps, void* x_out,
+                                    void* h_out, int rows, int c, int dtype, hipStream_t s) {
+  ETAINV_CHECK(y && ls_gamma && x && ln_gamma && ln_beta && h_out, "null pointer: y, ls_gamma, x, ln_gamma, ln_beta and h_out are required (x_out is optional)");
+  ETAINV_CHECK(dtype == ETAINV_F32 || dtype == ETAINV_F16 || dtype == ETAINV_BF16, "bad dtype");
+  ETAINV_CHECK(c >= 8 && c % 8 == 0 && (c >> 3) <= 192, "the width c must be a multiple of 8 and at most 1536");
+  ETAINV_CHECK(rows >= 0 && std::isfinite(eps) && eps >= 0.f, "rows must not be negative and eps finite and not negative");
+  ETAINV_CHECK((((uintptr_t)y | (uintptr_t)x | (uintptr_t)x_out | (uintptr_t)h_out | (uintptr_t)ls_gamma) & 15) == 0 &&
+                   (((uintptr_t)ln_gamma | (uintptr_t)ln_beta) & 3) == 0,
+               "y, x, x_out, h_out and ls_gamma must be 16-byte aligned, ln_gamma and ln_beta 4-byte aligned");
+  ETAINV_CHECK(h_out != x && h_out != y && h_out != x_out, "h_out must be a buffer of its own (x_out may be x)");
+  if (rows == 0) return 0;
+  ProfScope prof(PROF_LAYERNORM, (dtype == ETAINV_F32 ? 4.0 : 2.0) * (x_out ? 4.0 : 3.0) * (double)rows * c, s);
+  ETAINV_DISPATCH_DTYPE(dtype, T,
+                        hipLaunchKernelGGL(layerscale_add_layernorm_kernel<T>, dim3(cdiv(rows, 4)), dim3(256), 0, s, (const T*)y, ls_gamma, (const T*)x,
+                                           ln_gamma, ln_beta, (T*)x_out, (T*)h_out, rows, c, eps));
   ETAINV_LAUNCH_CHECK();
   return 0;
 }

@@ -58,6 +58,8 @@ SIGNATURES = {
     "etainv_op_gelu_erf": [_p, _p, _i64, _i, _p],
     "etainv_dino_selfsim_workspace_bytes": [_i, _i],
     "etainv_dino_selfsim_mse": [_p, _i, _i, _i, _i64, _f, _p, _p, _p, _i64, _i, _p],
+    "etainv_dinov2_preprocess": [_p, _i, _i, _i, _f, _f, _p, _p, _i, _p, _p, _i, _i, _p, _i, _p],
+    "etainv_op_layerscale_add_layernorm": [_p, _p, _p, _p, _p, _f, _p, _p, _i, _i, _i, _p],
     "etainv_lpips_preprocess": [_p, _p, _i, _i, _i, _i, _f, _f, _p, _i, _p],
     "etainv_op_conv2d_relu": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "etainv_op_maxpool3s2": [_p, _p, _i, _i, _i, _i, _i, _p],

@@ -405,7 +405,7 @@ def dino_geometry(state_dict, image=None):
     sd = state_dict
     bad = sorted({part for k in sd for part in k.split(".") if part in ("ls1", "ls2", "gamma_1", "gamma_2", "register_tokens")})
     if bad:
-        raise ValueError(f"a DINOv2 state dict ({', '.join(bad)}): LayerScale and register tokens are not built (dinovitstruct_v2)")
+        raise ValueError(f"a DINOv2 state dict ({', '.join(bad)}): LayerScale and register tokens are not built here (dinovitstruct_v2: dinov2_geometry, NativeDinov2Vision)")
     for k in ("patch_embed.proj.weight", "pos_embed", "cls_token"):
         if k not in sd:
             raise ValueError(f"not a DINO ViT state dict: {k} missing")
@@ -425,6 +425,129 @@ def dino_geometry(state_dict, image=None):
         raise ValueError(f"DINO tower: pos_embed has {n_pos} rows, expected 1 + ({image} / {p})^2 = {1 + (image // p) ** 2} (the position embeddings are "
                          f"not interpolated: the model runs at the image size it was trained at)")
     return {"width": d, "patch": p, "layers": layers, "image": image, "g2": (image // p) ** 2}
+
+
+DINOV2_PATCH, DINOV2_KP = 14, 640              # 3 * 14^2 = 588 values per patch row, padded with zeros to a whole number of 64-wide K steps
+
+
+def dinov2_geometry(state_dict, image=None):
+    """the sizes of a DINOv2 ViT state dict, read from its tensor shapes: width, patch (14), layers, `table` (the side M of the position grid:
+    37 for the published models, trained at 518), `image` (the side the model runs at; None: 224, or M * 14 when the table is smaller than
+    224 / 14 -- tiny models) and g2 = (image / 14)^2.  Refuses, with the reason, what the tower is not built for."""
+    sd = state_dict
+    if "register_tokens" in sd:
+        raise ValueError("DINOv2 tower: register tokens (the dinov2_vit*14_reg models) are not built")
+    if any(".mlp.w12." in k for k in sd):
+        raise ValueError("DINOv2 tower: the SwiGLU feed-forward of dinov2_vitg14 (mlp.w12, mlp.w3) is not built")
+    for k in ("patch_embed.proj.weight", "pos_embed", "cls_token", "blocks.0.ls1.gamma"):
+        if k not in sd:
+            raise ValueError(f"not a DINOv2 ViT state dict: {k} missing")
+    w, n_pos = sd["patch_embed.proj.weight"], sd["pos_embed"].shape[-2]
+    d = w.shape[0]
+    if d % 64:
+        raise ValueError(f"DINOv2 tower: width {d} is not a multiple of 64 (heads of 64 channels)")
+    if tuple(w.shape[-2:]) != (DINOV2_PATCH, DINOV2_PATCH):
+        raise ValueError(f"DINOv2 tower: patch size {tuple(w.shape[-2:])} must be 14 x 14")
+    m = math.isqrt(max(n_pos - 1, 0))
+    if m < 1 or n_pos != 1 + m * m:
+        raise ValueError(f"DINOv2 tower: pos_embed has {n_pos} rows, which is not 1 + M^2 for a square M x M position table")
+    layers = len({k.split(".")[1] for k in sd if k.startswith("blocks.")})
+    if image is None:
+        image = 224 if m >= 224 // DINOV2_PATCH else m * DINOV2_PATCH
+    if image < DINOV2_PATCH or image % DINOV2_PATCH:
+        raise ValueError(f"DINOv2 tower: the image side {image} must be a positive multiple of 14")
+    return {"width": d, "patch": DINOV2_PATCH, "layers": layers, "table": m, "image": image, "g2": (image // DINOV2_PATCH) ** 2}
+
+
+def dinov2_position_table(pos_embed, g, interpolate_offset=0.1):
+    """pos_embed [1][1 + M^2][d] -> float32 [1 + g^2][d] for a g x g patch grid, as the published DINOv2 `interpolate_pos_encoding` builds it:
+    the table as it is when g == M; otherwise, in float32, the M x M patch part through F.interpolate(mode="bicubic", antialias=False) with
+    scale_factor (g + offset) / M when `interpolate_offset` is not zero (torch then maps coordinates with 1 / scale_factor, not M / g) or with
+    size (g, g) when it is zero (transformers' Dinov2Model), behind the class row unchanged."""
+    import torch.nn.functional as F
+    pos = pos_embed.detach().float().reshape(-1, pos_embed.shape[-1])
+    m, d = math.isqrt(pos.shape[0] - 1), pos.shape[1]
+    if g == m:
+        return pos.contiguous()
+    grid = pos[1:].reshape(1, m, m, d).permute(0, 3, 1, 2)
+    if interpolate_offset:
+        sf = float(g + interpolate_offset) / m
+        out = F.interpolate(grid, mode="bicubic", antialias=False, scale_factor=(sf, sf))
+    else:
+        out = F.interpolate(grid, mode="bicubic", antialias=False, size=(g, g))
+    if tuple(out.shape[-2:]) != (g, g):
+        raise ValueError(f"DINOv2 tower: interpolate_offset {interpolate_offset} gives a {tuple(out.shape[-2:])} position grid, not {g} x {g}")
+    return torch.cat([pos[:1], out.permute(0, 2, 3, 1).reshape(g * g, d)]).contiguous()
+
+
+class NativeDinov2Vision:
+    """DINOv2's ViT (dinov2_vits14 / vitb14 / vitl14: the names of the published checkpoints) up to the keys of its last block.  Over
+    NativeDinoVision: patch 14 on rows of DINOV2_KP = 640 (etainv_dinov2_preprocess; the patch weight is padded with zero columns), a position table
+    interpolated ONCE here, on the host, for the grid the model runs at (dinov2_position_table: the call the published model makes), and
+    LayerScale: x = x + ls.gamma * branch(x).  The branch's last GEMM runs without residual and etainv_op_layerscale_add_layernorm applies
+    gamma in fp32, adds, stores x and writes the NEXT LayerNorm's output in the same pass; gamma is never folded into the 16-bit weights.
+    Launches for L blocks: ln (block 0's norm1), then per block qkv, attention, proj, fused (ls1, norm2), fc1, gelu, fc2, fused (ls2, next
+    norm1); block L-2's last fusion stores no x; block L-1 is the key third of its qkv GEMM."""
+
+    def __init__(self, state_dict, compute_dtype=torch.float16, interpolate_offset=0.1, image=None):
+        import torch.nn.functional as F
+        gm = dinov2_geometry(state_dict, image)
+        d, layers = gm["width"], gm["layers"]
+        self.ops, self.cd, self.d, self.heads, self.patch, self.image, self.g2 = _Ops(compute_dtype), compute_dtype, d, d // 64, 14, gm["image"], gm["g2"]
+        self.table, self.interpolate_offset, self.kp = gm["table"], float(interpolate_offset), DINOV2_KP
+        f32 = torch.float32
+        g = lambda name, shape: self._get(state_dict, name, shape)
+        self.patch_w = _dev(F.pad(g("patch_embed.proj.weight", (d, 3, 14, 14)).reshape(d, 588), (0, DINOV2_KP - 588)), compute_dtype)
+        self.patch_b = _dev(g("patch_embed.proj.bias", (d,)), f32)
+        self.cls = _dev(g("cls_token", (1, 1, d)).reshape(d), compute_dtype)
+        self.pos = _dev(dinov2_position_table(g("pos_embed", (1, gm["table"] ** 2 + 1, d)), math.isqrt(self.g2), self.interpolate_offset), compute_dtype)
+        lin = lambda name, o, k: (_dev(g(name + ".weight", (o, k)), compute_dtype), _dev(g(name + ".bias", (o,)), f32))
+        ln = lambda name: (_dev(g(name + ".weight", (d,)), f32), _dev(g(name + ".bias", (d,)), f32))
+        self.first_ln = ln("blocks.0.norm1")
+        self.layers = []
+        for i in range(layers - 1):
+            p = f"blocks.{i}."
+            self.layers.append({"qkv": lin(p + "attn.qkv", 3 * d, d), "out": lin(p + "attn.proj", d, d), "ls1": _dev(g(p + "ls1.gamma", (d,)), f32),
+                                "ln2": ln(p + "norm2"), "fc1": lin(p + "mlp.fc1", 4 * d, d), "fc2": lin(p + "mlp.fc2", d, 4 * d),
+                                "ls2": _dev(g(p + "ls2.gamma", (d,)), f32), "next_ln1": ln(f"blocks.{i + 1}.norm1")})
+        p = f"blocks.{layers - 1}."
+        self.key_w = _dev(g(p + "attn.qkv.weight", (3 * d, d))[d:2 * d], compute_dtype)
+        self.key_b = _dev(g(p + "attn.qkv.bias", (3 * d,))[d:2 * d], f32)
+
+    @staticmethod
+    def _get(sd, name, shape):
+        if name not in sd:
+            raise ValueError(f"DINOv2 state dict: {name} missing")
+        t = sd[name].float()
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"DINOv2 state dict: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+        return t
+
+    def ls_ln(self, y, ls, x, ln, store_x=True):
+        """x <- x + ls * y in place (unless store_x is False) and LayerNorm of the stored sum, one launch; returns the LayerNorm's output"""
+        o = self.ops
+        h = torch.empty_like(x)
+        _capi.check(o.lib.etainv_op_layerscale_add_layernorm(_capi.ptr(y), _capi.ptr(ls), _capi.ptr(x), _capi.ptr(ln[0]), _capi.ptr(ln[1]), 1e-6,
+                                                             _capi.ptr(x) if store_x else None, _capi.ptr(h), x.shape[0], x.shape[1], o.code, o.st()))
+        return h
+
+    def __call__(self, rows, b):
+        """patch rows [b g^2][640] (compute dtype, from etainv_dinov2_preprocess) -> the last block's keys [b][1 + g^2][d] (compute dtype)"""
+        o, d, n = self.ops, self.d, self.g2 + 1
+        assert rows.shape == (b * self.g2, self.kp) and rows.dtype == self.cd, (rows.shape, rows.dtype)
+        pe = o.gemm(rows, self.patch_w, self.patch_b)
+        x = torch.empty(b * n, d, dtype=self.cd, device="cuda")
+        _capi.check(o.lib.etainv_clip_assemble_tokens(_capi.ptr(pe), _capi.ptr(self.cls), _capi.ptr(self.pos), _capi.ptr(x), b, self.g2, d, o.code, o.st()))
+        h = o.ln(x, *self.first_ln, eps=1e-6)
+        for i, l in enumerate(self.layers):
+            qkv = o.gemm(h, *l["qkv"])
+            att = torch.empty(b * n, d, dtype=self.cd, device="cuda")
+            _capi.check(o.lib.etainv_op_vit_attention(_capi.ptr(qkv), _capi.ptr(att), b, n, self.heads, 64, o.code, o.st()))
+            h = self.ls_ln(o.gemm(att, *l["out"]), l["ls1"], x, l["ln2"])
+            f = o.gemm(h, *l["fc1"])
+            _capi.check(o.lib.etainv_op_gelu_erf(_capi.ptr(f), _capi.ptr(f), f.numel(), o.code, o.st()))
+            h = self.ls_ln(o.gemm(f, *l["fc2"]), l["ls2"], x, l["next_ln1"], store_x=i < len(self.layers) - 1)
+        return o.gemm(h, self.key_w, self.key_b).reshape(b, n, d)
 
 
 def clip_geometry(state_dict):

@@ -205,7 +205,7 @@ def load_dino_state_dict(path) -> dict:
     """The DINO ViT state dict at `path` (or the dict given), fp32, under the names of DINO's published backbone checkpoints (`cls_token`,
     `pos_embed`, `patch_embed.proj`, `blocks.N.*`).  A full training checkpoint is unwrapped (`teacher`, else `state_dict`) and the prefixes
     `module.` and `backbone.` are stripped; the projection head's tensors are dropped.  DINOv2 state dicts (LayerScale, register tokens) are
-    refused: that model is `dinovitstruct_v2`, which is not built."""
+    refused: that model is `dinovitstruct_v2`'s (`load_dinov2_state_dict`)."""
     sd = path if isinstance(path, dict) else torch.load(str(path), map_location="cpu", weights_only=True)
     for wrap in ("teacher", "state_dict"):
         if wrap in sd and isinstance(sd[wrap], dict):
@@ -222,10 +222,73 @@ def load_dino_state_dict(path) -> dict:
     bad = sorted({part for k in out for part in k.split(".") if part in _DINO_V2_KEYS})
     if bad:
         raise ValueError(f"a DINOv2 state dict ({', '.join(bad)}): dinovitstruct takes the DINO ViT checkpoints; dinovitstruct_v2 (patch 14, LayerScale, "
-                         f"interpolated position embeddings) is not built")
+                         f"interpolated position embeddings) is not built here: load_dinov2_state_dict")
     missing = [k for k in ("cls_token", "pos_embed", "patch_embed.proj.weight", "patch_embed.proj.bias", "blocks.0.attn.qkv.weight") if k not in out]
     if missing:
         raise ValueError(f"not a DINO ViT state dict: {', '.join(missing)} missing")
+    return out
+
+
+# ---- DINOv2 (the dinovitstruct_v2 metric's model): the names of the published dinov2_vit{s,b,l}14 backbone checkpoints
+def synthetic_dinov2_state_dict(width=768, layers=12, patch=14, image=224, table=37, seed=0) -> dict:
+    """every parameter the DINOv2 tower reads, synthetic: the DINO recipe (class token and position embeddings 0.5 N(0, 1), everything else
+    `synthetic_tensor`) over a position table of `table` x `table` patches, plus the LayerScale vectors `blocks.N.ls{1,2}.gamma`: magnitudes
+    log-uniform in [1e-5, 1] (DINOv2 initialises them at 1e-5 and trained values span that range), random sign.  `image` is where the model
+    runs (dinov2_geometry); it does not shape any tensor."""
+    del image
+    d = width
+    shapes = {"cls_token": (1, 1, d), "pos_embed": (1, table * table + 1, d), "patch_embed.proj.weight": (d, 3, patch, patch),
+              "patch_embed.proj.bias": (d,), "norm.weight": (d,), "norm.bias": (d,), "mask_token": (1, d)}
+    for i in range(layers):
+        p = f"blocks.{i}."
+        for lin, (o, k) in {"attn.qkv": (3 * d, d), "attn.proj": (d, d), "mlp.fc1": (4 * d, d), "mlp.fc2": (d, 4 * d)}.items():
+            shapes[p + lin + ".weight"], shapes[p + lin + ".bias"] = (o, k), (o,)
+        for ln in ("norm1", "norm2"):
+            shapes[p + ln + ".weight"] = shapes[p + ln + ".bias"] = (d,)
+        shapes[p + "ls1.gamma"] = shapes[p + "ls2.gamma"] = (d,)
+    out = {}
+    for name, shape in shapes.items():
+        g = torch.Generator().manual_seed((zlib.crc32(("dinov2." + name).encode()) + 1000003 * seed) & 0x7FFFFFFF)
+        if name in ("cls_token", "pos_embed"):
+            out[name] = 0.5 * torch.randn(shape, generator=g)
+        elif name.endswith(".gamma"):
+            sign = torch.randint(0, 2, shape, generator=g).float() * 2 - 1
+            out[name] = sign * torch.pow(10.0, -5.0 * torch.rand(shape, generator=g))
+        elif name == "mask_token":
+            out[name] = torch.zeros(shape)
+        else:
+            out[name] = synthetic_tensor("dinov2." + name, shape, seed)
+    return out
+
+
+def load_dinov2_state_dict(path) -> dict:
+    """The DINOv2 ViT state dict at `path` (or the dict given), fp32, under the names of the published backbone checkpoints (`cls_token`,
+    `pos_embed`, `patch_embed.proj`, `blocks.N.{norm1, attn, ls1, norm2, mlp, ls2}`).  Unwrapped and stripped as `load_dino_state_dict` does;
+    `head.*` is dropped.  Required: `blocks.0.ls1.gamma` (a DINO checkpoint goes to `load_dino_state_dict`).  Refused, with the reason: the
+    register-token models (`register_tokens`) and dinov2_vitg14 (SwiGLU: `mlp.w12`)."""
+    sd = path if isinstance(path, dict) else torch.load(str(path), map_location="cpu", weights_only=True)
+    for wrap in ("teacher", "state_dict"):
+        if wrap in sd and isinstance(sd[wrap], dict):
+            sd = sd[wrap]
+            break
+    out = {}
+    for k, v in sd.items():
+        for pre in ("module.", "backbone."):
+            if k.startswith(pre):
+                k = k[len(pre):]
+        if k.startswith("head.") or not torch.is_tensor(v) or not v.is_floating_point():
+            continue
+        out[k] = v.detach().float()
+    if "register_tokens" in out:
+        raise ValueError("a DINOv2 state dict with register_tokens: the register-token models (dinov2_vit*14_reg) are not built (they also "
+                         "interpolate their position embeddings with antialiasing and without the 0.1 offset)")
+    if any(".mlp.w12." in k or ".mlp.w3." in k for k in out):
+        raise ValueError("a DINOv2 state dict with mlp.w12 / mlp.w3: dinov2_vitg14's SwiGLU feed-forward is not built (vits14, vitb14 and vitl14 are)")
+    missing = [k for k in ("cls_token", "pos_embed", "patch_embed.proj.weight", "patch_embed.proj.bias", "blocks.0.attn.qkv.weight", "blocks.0.ls1.gamma")
+               if k not in out]
+    if missing:
+        raise ValueError(f"not a DINOv2 ViT state dict: {', '.join(missing)} missing (a DINO checkpoint without LayerScale is dinovitstruct's: "
+                         f"load_dino_state_dict)")
     return out
 
 

@@ -10,6 +10,10 @@ antialiased bilinear interpolation, restated as per-output tables built in float
 the ImageNet normalisation, the tower up to `blocks[L-1].attn.qkv`, its key third, `attn_cosine_sim` (the clamp is on the product of the norms) and
 the mean squared difference.
 
+dinovitstruct_v2 is the same metric on a DINOv2 ViT (`Dinov2Model`: patch 14, LayerScale, position embeddings interpolated from the 37 x 37
+table the model was trained with; reference :32-34, :120-122, :141-160): etainv_dinov2_preprocess, NativeDinov2Vision with the fused
+etainv_op_layerscale_add_layernorm, and the same self-similarity call.
+
 Weights are handed over explicitly (`weights=`: a path, a state dict, a loaded `DinoModel`, or "synthetic"); there is no default and no download.
 Images must be square: DINO interpolates its position embeddings bicubically for any other shape, which is not built."""
 import functools
@@ -31,6 +35,13 @@ GEOMETRY = {
     "dino_vits16": dict(width=384, layers=12, patch=16, image=224),
     "tiny/8": dict(width=128, layers=2, patch=8, image=32),         # synthetic weights only: quick runs
 }
+GEOMETRY_V2 = {
+    "dinov2_vits14": dict(width=384, layers=12, patch=14, image=224, table=37),
+    "dinov2_vitb14": dict(width=768, layers=12, patch=14, image=224, table=37),
+    "dinov2_vitl14": dict(width=1024, layers=24, patch=14, image=224, table=37),
+    "tinyv2/14": dict(width=128, layers=2, patch=14, image=42, table=5),      # synthetic weights only: 10 tokens, the table interpolated 5 -> 3
+}
+V2_KP = 640                           # a patch-14 row: 588 values and 52 zeros (etainv_dinov2_preprocess)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the resize tables
@@ -139,6 +150,40 @@ def dino_preprocess(x: torch.Tensor, input_range=(-1, 1), r: int = 224, p: int =
     return rows
 
 
+def dinov2_preprocess(x: torch.Tensor, input_range=(-1, 1), r: int = 224, dtype=torch.float16, antialias: bool = True) -> torch.Tensor:
+    """`dino_preprocess` for DINOv2's patch 14: (B, 3, S, S) -> patch rows [B (r / 14)^2][640] in `dtype`, element k = c 196 + py 14 + px for
+    k < 588 and zero behind.  Device tensors: one etainv_dinov2_preprocess launch; CPU tensors: float32 torch."""
+    _check_images_v2(x, r)
+    lo, hi = _range(input_range)
+    s = x.shape[-1]
+    if not x.is_cuda:
+        bounds, coef = resize_tables(s, r, antialias)
+        v = (x.detach().float() - lo) / (hi - lo)
+        v = _resample_torch(_resample_torch(v, bounds, coef).transpose(-1, -2), bounds, coef).transpose(-1, -2)
+        v = (v - torch.tensor(MEAN).view(1, 3, 1, 1)) / torch.tensor(STD).view(1, 3, 1, 1)
+        return F.pad(_patch_rows(v, 14), (0, V2_KP - 588)).contiguous().to(dtype)
+    from etainv import _capi
+    lib = _capi.load()
+    x = x.detach().to(torch.float32).contiguous()
+    b, g = x.shape[0], r // 14
+    tb, tc, ksize, band = _device_tables(s, r, 14, bool(antialias), str(x.device))
+    with torch.cuda.device(x.device):
+        rows = torch.empty(b * g * g, V2_KP, dtype=dtype, device=x.device)
+        _capi.check(lib.etainv_dinov2_preprocess(_capi.ptr(x), b, s, r, lo, hi, _capi.ptr(tb), _capi.ptr(tc), ksize, _capi.ptr(tb), _capi.ptr(tc), ksize,
+                                                 band, _capi.ptr(rows), _capi.dtype_code(dtype), _capi.stream_ptr()))
+    return rows
+
+
+def _check_images_v2(x: torch.Tensor, r: int) -> None:
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"Input images should be (B, 3, H, W) tensors, but got {tuple(x.shape)}")
+    if x.shape[2] != x.shape[3]:
+        raise ValueError(f"dinovitstruct_v2 takes square images (the other shapes resize to sides that are no multiples of 14, which DINOv2's own patch "
+                         f"embedding refuses), but got {tuple(x.shape[2:])}")
+    if r < 14 or r % 14:
+        raise ValueError(f"the model's image size {r} must be a multiple of the patch size 14")
+
+
 # ---------------------------------------------------------------------------------------------------------------- the float32 torch tower
 class _TorchDino:
     """the tower in plain float32 torch on the CPU, over DINO's checkpoint names"""
@@ -166,6 +211,36 @@ class _TorchDino:
             a = (q @ k.transpose(-1, -2) * 0.125).softmax(-1) @ v
             x = x + lin(a.transpose(1, 2).reshape(b, n, d), p + "attn.proj")
             x = x + lin(F.gelu(lin(ln(x, p + "norm2"), p + "mlp.fc1")), p + "mlp.fc2")
+
+
+class _TorchDinov2:
+    """the DINOv2 tower in plain float32 torch on the CPU, over the published checkpoint names"""
+
+    def __init__(self, sd: dict, interpolate_offset: float = 0.1, image=None):
+        from etainv.nets import dinov2_geometry, dinov2_position_table
+        gm = dinov2_geometry(sd, image)
+        self.sd = {k: v.float() for k, v in sd.items()}
+        self.d, self.patch, self.image, self.g2, self.depth, self.table = gm["width"], 14, gm["image"], gm["g2"], gm["layers"], gm["table"]
+        self.interpolate_offset = float(interpolate_offset)
+        self.pos = dinov2_position_table(self.sd["pos_embed"], self.image // 14, self.interpolate_offset)
+
+    def __call__(self, rows: torch.Tensor, b: int) -> torch.Tensor:
+        sd, d, heads = self.sd, self.d, self.d // 64
+        lin = lambda t, name: F.linear(t, sd[name + ".weight"], sd[name + ".bias"])
+        ln = lambda t, name: F.layer_norm(t, (d,), sd[name + ".weight"], sd[name + ".bias"], eps=1e-6)
+        pe = F.linear(rows.float()[:, :588], sd["patch_embed.proj.weight"].reshape(d, -1), sd["patch_embed.proj.bias"]).reshape(b, -1, d)
+        x = torch.cat([sd["cls_token"].reshape(1, 1, d).expand(b, 1, d), pe], 1) + self.pos[None]
+        n = x.shape[1]
+        sp = lambda t: t.reshape(b, n, heads, 64).transpose(1, 2)
+        for i in range(self.depth):
+            p = f"blocks.{i}."
+            h = ln(x, p + "norm1")
+            if i == self.depth - 1:
+                return F.linear(h, sd[p + "attn.qkv.weight"][d:2 * d], sd[p + "attn.qkv.bias"][d:2 * d])
+            q, k, v = (sp(t) for t in lin(h, p + "attn.qkv").split(d, -1))
+            a = (q @ k.transpose(-1, -2) * 0.125).softmax(-1) @ v
+            x = x + sd[p + "ls1.gamma"] * lin(a.transpose(1, 2).reshape(b, n, d), p + "attn.proj")
+            x = x + sd[p + "ls2.gamma"] * lin(F.gelu(lin(ln(x, p + "norm2"), p + "mlp.fc1")), p + "mlp.fc2")
 
 
 # ---------------------------------------------------------------------------------------------------------------- the model
@@ -215,6 +290,54 @@ class DinoModel:
         return self.backend(dino_preprocess(x, input_range, self.image, self.patch, torch.float32, self.antialias), x.shape[0])
 
 
+class Dinov2Model:
+    """A loaded DINOv2 ViT for dinovitstruct_v2: the surface of `DinoModel` (keys(), a loaded model is shared, "synthetic")."""
+
+    def __init__(self, weights, device: Optional[str] = None, dino_model: str = "dinov2_vitb14", compute_dtype=torch.float16, antialias: bool = True,
+                 interpolate_offset: float = 0.1, seed: int = 0, image: Optional[int] = None):
+        """`weights`: a path to a published dinov2_vit{s,b,l}14 backbone checkpoint, a state dict, a loaded `Dinov2Model` (shared as it is), or
+        "synthetic" (then `dino_model` picks the geometry from GEOMETRY_V2).  `interpolate_offset`: 0.1 is the published hub models' way of
+        interpolating the position table (scale_factor (g + 0.1) / M); 0 is transformers' (size (g, g)).  `image`: the side the model runs at
+        (None: 224, the reference's Resize; the model's own side for tables smaller than 16 x 16)."""
+        from etainv.weights import load_dinov2_state_dict, synthetic_dinov2_state_dict
+        if isinstance(weights, Dinov2Model):
+            self.__dict__.update(weights.__dict__)
+            return
+        if weights is None:
+            raise ValueError("dinovitstruct_v2 needs weights=: a path, a state dict or \"synthetic\" (there is no default and no download)")
+        if device is None:
+            device = "cuda" if torch.cuda.is_available() else "cpu"
+        if dino_model in ("dinov2_vitg14",) or dino_model.endswith("_reg"):
+            raise NotImplementedError(f"{dino_model}: the SwiGLU feed-forward of dinov2_vitg14 and the register-token models are not built")
+        self.device, self.name, self.antialias = str(device), dino_model, bool(antialias)
+        self.synthetic = isinstance(weights, str) and weights == "synthetic"
+        if self.synthetic:
+            if dino_model not in GEOMETRY_V2:
+                raise ValueError(f"dino_model must be one of {', '.join(GEOMETRY_V2)} for synthetic weights, got {dino_model}")
+            sd = synthetic_dinov2_state_dict(seed=seed, **GEOMETRY_V2[dino_model])
+            image = GEOMETRY_V2[dino_model]["image"] if image is None else image
+        else:
+            sd = load_dinov2_state_dict(weights)
+        if self.device.startswith("cuda"):
+            from etainv.nets import NativeDinov2Vision
+            with torch.cuda.device(self.device):
+                self.backend = NativeDinov2Vision(sd, compute_dtype=compute_dtype, interpolate_offset=interpolate_offset, image=image)
+            self.dtype = compute_dtype
+        else:
+            self.backend, self.dtype = _TorchDinov2(sd, interpolate_offset, image), torch.float32
+        self.patch, self.image, self.width, self.table = 14, self.backend.image, self.backend.d, self.backend.table
+        self.interpolate_offset = float(interpolate_offset)
+
+    def keys(self, x: torch.Tensor, input_range=(-1, 1)) -> torch.Tensor:
+        """(B, 3, S, S) -> the last block's attention keys [B][n][d], n = 1 + (image / 14)^2, in the model's dtype on its device"""
+        x = x.to(self.device)
+        _check_images_v2(x, self.image)
+        if x.is_cuda:
+            with torch.cuda.device(x.device):
+                return self.backend(dinov2_preprocess(x, input_range, self.image, self.dtype, self.antialias), x.shape[0])
+        return self.backend(dinov2_preprocess(x, input_range, self.image, torch.float32, self.antialias), x.shape[0])
+
+
 def key_self_similarity_mse(keys: torch.Tensor, eps: float = EPS, d: Optional[int] = None, return_norms: bool = False):
     """keys [2 B][n][ld] (rows 0 .. B-1 the sources', B .. 2B-1 the edits'; the first `d` columns of every row are used, default all) ->
     float64 [B]: the mean over all n^2 token pairs of the squared difference of the two cosine self-similarity matrices.  Device tensors: one
@@ -246,8 +369,9 @@ def key_self_similarity_mse(keys: torch.Tensor, eps: float = EPS, d: Optional[in
     return (out, norms) if return_norms else out
 
 
-def dino_structure(edit: torch.Tensor, source: torch.Tensor, model: DinoModel, input_range=(-1, 1)) -> torch.Tensor:
-    """float64 [B] structure distances of B pairs: `edit` the edited images, `source` the input images, both (B, 3, S, S) in `input_range`.  One
+def dino_structure(edit: torch.Tensor, source: torch.Tensor, model, input_range=(-1, 1)) -> torch.Tensor:
+    """float64 [B] structure distances of B pairs under `model`, a `DinoModel` (dinovitstruct) or a `Dinov2Model` (dinovitstruct_v2): `edit`
+    the edited images, `source` the input images, both (B, 3, S, S) in `input_range`.  One
     preprocess launch and one tower pass for the 2 B images, one self-similarity call.  Every pair is independent: row i is what a call with
     pair i alone returns."""
     if edit.shape != source.shape:
@@ -262,10 +386,16 @@ class DinoVitStructure(SimpleMetric):
 
     def __init__(self, input_range: Tuple[int, int] = (-1, 1), device: Optional[str] = None, vit_model: Optional[str] = "dino_vitb8", weights=None,
                  antialias: bool = True) -> None:
-        """`vit_model`: dino_vitb8, dino_vits8, dino_vitb16 or dino_vits16.  `weights`: a path, a state dict, a loaded `DinoModel` or "synthetic"."""
+        """`vit_model`: dino_vitb8, dino_vits8, dino_vitb16 or dino_vits16, or (dinovitstruct_v2) dinov2_vits14, dinov2_vitb14 or dinov2_vitl14.
+        `weights`: a path, a state dict, a loaded `DinoModel` / `Dinov2Model` or "synthetic"."""
         super().__init__(input_range, device)
         self.vit_model = vit_model
-        self.model = weights if isinstance(weights, DinoModel) else DinoModel(weights, self.device, vit_model, antialias=antialias)
+        if isinstance(weights, (DinoModel, Dinov2Model)):
+            self.model = weights
+        elif vit_model.startswith("dinov2") or vit_model in GEOMETRY_V2:
+            self.model = Dinov2Model(weights, self.device, vit_model, antialias=antialias)
+        else:
+            self.model = DinoModel(weights, self.device, vit_model, antialias=antialias)
         self.losses = []
 
     def forward(self, pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:

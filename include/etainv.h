@@ -268,6 +268,26 @@ int64_t etainv_dino_selfsim_workspace_bytes(int b, int n);
 int etainv_dino_selfsim_mse(const void* keys, int b, int n, int d, int64_t ld, float eps, double* scores_out, float* norms_out, void* workspace,
                             int64_t workspace_bytes, int dtype, void* stream);
 
+/* ---- dinovitstruct_v2 (reference metrics/dino_vit_structure.py:32-34, :120-122, :141-160: the same metric on a DINOv2 ViT, patch 14): what the
+ * DINOv2 tower needs beyond the dinovitstruct section above.  Its position embeddings are interpolated once per model on the host.
+ *
+ * etainv_dinov2_preprocess: etainv_dino_preprocess for patch 14.  rows_out [b (r / 14)^2][ETAINV_DINOV2_KP] in `dtype`: element
+ *   k = c 196 + py 14 + px for k < 588; columns 588 .. 639 are written as zero (588 is no whole number of GEMM K steps; the patch weight is
+ *   padded to match).  Tables, clamping and the LDS need (max_rows * r * 4 bytes, at most 65536) are those of etainv_dino_preprocess.
+ *   Refused: a null or misaligned pointer, r not a multiple of 14, b above 65535, hi <= lo, a band that does not fit.
+ * etainv_op_layerscale_add_layernorm: DINOv2's residual step x + ls.gamma * branch(x) and the LayerNorm behind it, in one pass.  Per row of c:
+ *   x_out = x + ls_gamma * y with one fp32 FMA per element, rounded once to `dtype`; h_out = LayerNorm(x_out AS STORED; ln_gamma, ln_beta, eps),
+ *   exact two-pass mean and variance in fp32.  In fp16 and bf16, h_out equals etainv_op_layernorm(x_out) bit for bit.  ls_gamma stays fp32: it is
+ *   never folded into 16-bit weights (trained values reach 1e-5 and below).  x_out may be null (h_out alone is written) and may be x (in
+ *   place: a wave reads its whole row before it writes); h_out is required and must be a buffer of its own.  One wave per row, fixed summation
+ *   order, no atomics: bit-identical from run to run.  Refused: a null y / ls_gamma / x / ln_gamma / ln_beta / h_out, c not a multiple of 8 or
+ *   above 1536, y / x / x_out / h_out / ls_gamma not 16-byte aligned. */
+#define ETAINV_DINOV2_KP 640
+int etainv_dinov2_preprocess(const float* x, int b, int s, int r, float lo, float hi, const int32_t* bounds_h, const float* coef_h, int ksize_h,
+                             const int32_t* bounds_v, const float* coef_v, int ksize_v, int max_rows, void* rows_out, int dtype, void* stream);
+int etainv_op_layerscale_add_layernorm(const void* y, const float* ls_gamma, const void* x, const float* ln_gamma, const float* ln_beta, float eps,
+                                       void* x_out, void* h_out, int rows, int c, int dtype, void* stream);
+
 /* ---- lpips, bglpips (reference metrics/metrics.py:40-61, metrics/bglpips.py:27-52 and :141-148; LPIPS v0.1, net='alex', lpips=True,
  * spatial=False, eval mode): image preprocessing, the AlexNet tower's convolution and pooling, and the per-tap distance.
  *
